@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py — batched cartpole++ env-steps/sec on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]                       # C3 (default)
+    python bench.py [--gpus N --steps K --warmup W]                       # C3 (default): the headline only
+    python bench.py --full                                                # + every other leg (below)
+    python bench.py --dump-outputs DIR                                    # + the last timed step's outputs
     python bench.py --continuous --batch 4096                             # C2
     python bench.py --raster                                              # C5
     python bench.py --gpus N                                              # C4: launches N ranks itself
@@ -27,18 +29,31 @@ A "step" is one env-step of every env: one cp_step call = one fused R-substep ke
 launch + one compacted reset launch.  Actions are pre-generated in HBM (a hash of
 (seed, global env id, step, cart)), so sharded runs see the unsharded job's actions.
 
+A plain run does what the headline needs and no more: set up, W untimed steps, the K timed
+steps, the outputs when --dump-outputs is given, the JSON line (value, ms_per_step, the
+roofline from the timed window's own HIP events).  Every leg that takes GPU or CPU runs of its
+own is behind --full: median5, steady_state, secondary, cpu_baseline, gym_mirror_b1_gpu and
+parity, each as described below and each still switched off by its --no-* option.
+
+--dump-outputs DIR: after the timed window, what its last step handed to the caller, as
+DIR/<name>.npy (obs, reward, done, terminal_obs with autoreset on, pixels with --raster; all
+float32, which holds every output type exactly; rank 0's shard).  An array that would take the
+dump past 64 MB is written as a sample: the elements at DUMP_SEED's sorted flat indices (dump_sample).
+Bumps and actions are functions of the seed alone, so equal arguments give equal inputs.
+
 Timing: W untimed steps, then EXACTLY K steps between barrier + synchronize; value =
 N*B*K / max-over-ranks wall.  A K-step window need not contain an autoreset burst (every
 episode is 200 steps) or, at N > 1, a return gather; so the line also reports
-resets_in_window, collectives_in_window, and a steady_state sub-object: one more full
+resets_in_window, collectives_in_window, and (--full) a steady_state sub-object: one more full
 200-step cycle (its reset burst and one gather included) timed the same way.
-SURVEY.md §8d's "median of 5 runs": `median5` holds the headline window and 4 more K-step
+SURVEY.md §8d's "median of 5 runs" (--full): `median5` holds the headline window and 4 more K-step
 windows right after it (same definition as value, each its own barrier + synchronize), and
 steady_state.median5 five consecutive 200-step cycles; value itself stays the first window.
 
 roofline: the step kernel's algorithmic HBM bytes per launch over its
 average duration from HIP events recorded on its launch stream in the timed region
 (every 4th launch sampled: the events themselves cost wall time).
+The legs below run with --full only.
 cpu_baseline (rank 0, N = 1): the oracle (a port: same algorithm, gcc -O3 -march=native,
 the kernel's results) on bounded samples: C3 on every CPU of the process's affinity mask
 (OpenMP; `value`), on 16 threads and on one core, and C1.
@@ -395,6 +410,55 @@ def timed(env, actions, t0, K, world, dev, gather_at_end, rollout=0):
     return float(el.item()), hist, gathers
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_SEED = 1234
+DUMP_MAX_BYTES = 62_000_000   # array bytes of the whole dump: under 64 MB with the .npy headers and the directory
+
+
+def last_outputs(env):
+    """What the last step() / rollout() handed to its caller: obs, reward and done (after a rollout
+    the handle's step-level attributes hold its last step's values), the terminal obs when autoreset
+    collects it, the raster obs when it is on.  A StreamShards batch is its shards in env order."""
+    envs = env.envs if isinstance(env, StreamShards) else [env]
+    out = {}
+    for name in ("obs", "reward", "done", "terminal_obs", "pixels"):
+        ts = [getattr(e, name) for e in envs]
+        if ts[0] is not None:
+            out[name] = ts[0] if len(ts) == 1 else torch.cat(ts)
+    return out
+
+
+def dump_sample(t, max_elems, seed=DUMP_SEED):
+    """t itself when it has at most max_elems elements, else its elements at max_elems flat indices
+    drawn (with replacement, then sorted) by a CPU generator seeded with `seed`: a function of
+    (seed, t.numel(), max_elems) alone, so two builds sample the same elements."""
+    n = t.numel()
+    if n <= max_elems:
+        return t
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, n, (max_elems,), generator=g, dtype=torch.int64).sort().values
+    return t.reshape(-1)[idx.to(t.device)]
+
+
+def dump_outputs(outs, path, max_bytes=DUMP_MAX_BYTES):
+    """Write {name: tensor} as path/<name>.npy in float32, the smallest arrays first and whole; an
+    array larger than its share of the bytes still free is written as dump_sample's sample.
+    -> {name: {"shape", "of"}} ("of": the full array's shape when the file holds a sample)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left, wrote = max_bytes, {}
+    names = sorted(outs, key=lambda k: outs[k].numel())
+    for i, name in enumerate(names):
+        t = outs[name]
+        share = left // (len(names) - i)
+        s = dump_sample(t, t.numel() if t.numel() * 4 <= share else share // 4)
+        a = s.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+        wrote[name] = {"shape": list(a.shape), **({"of": list(t.shape)} if s is not t else {})}
+    return wrote
+
+
 # ----------------------------------------------------------------- CPU legs
 def host_cpus():
     """The CPUs this process may actually use: the affinity mask, capped by the cgroup CPU quota
@@ -694,7 +758,7 @@ def parity_check(device, R, shape, B=128, steps=WINDOW):
 
 
 # ------------------------------------------------------------ secondary lines
-# Configurations other than the headline, measured inside the default run (rank 0, N = 1) so the
+# Configurations other than the headline, measured inside the default --full run (rank 0, N = 1) so the
 # driver's own run observes them: each on a fresh handle, reset + W untimed steps, then K steps
 # timed like the headline (synchronize on both sides).  (name, envs, steps, kwargs, continuous,
 # rollout K): the BASELINE.json configs and the modes DESIGN.md §5 reports.
@@ -837,6 +901,12 @@ def main():
     ap.add_argument("--continuous", action="store_true", help="C2: continuous (B,2,2) U[-1,1] actions")
     ap.add_argument("--dtype", choices=("f32", "f64"), default="f32",
                     help="f64: the fp64 kernel variant (cp_config.precision; the parity mode, DESIGN.md §7)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg: median5, steady_state, secondary, cpu_baseline, "
+                         "gym_mirror_b1_gpu and parity (minutes; each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (obs, reward, done, ...) as DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (a seeded sample of a larger array)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the cpu_baseline, parity and secondary legs (profiling runs: only the headline's kernels)")
     ap.add_argument("--no-parity", action="store_true")
@@ -921,8 +991,8 @@ def main():
         env.set_kernel_shape(args.shape, args.reset_shape or args.shape)
     if args.raster:
         env.enable_raster(True, num_cameras=args.cameras)
-    ss_steps = 0 if args.no_steady_state else WINDOW
-    n_med = 1 if args.no_median else 5
+    ss_steps = WINDOW if args.full and not args.no_steady_state else 0
+    n_med = 5 if args.full and not args.no_median else 1
     actions = make_actions(args.continuous, B, spec["env_id_offset"], W + n_med * (K + ss_steps), SEED, dev)
     env.reset()
     if args.rollout and args.streams == 1:   # the rollout kernel loaded, its output buffers allocated (~2 GB)
@@ -949,6 +1019,8 @@ def main():
     enqueue_ms = LAST_ENQUEUE_S / K * 1e3
     tm = env.timing_end()
     simulated, resets = simulated_steps(env, B, K, ep0, p0, next_step)
+    # the timed window's last step, before any --full window steps on
+    dumped = dump_outputs(last_outputs(env), args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     def window(t0, n):
         """One more n-step window from step t0, timed like the headline: (value over ranks, seconds,
@@ -1075,6 +1147,7 @@ def main():
         "build": {"lib": os.path.relpath(native_lib_path(), ROOT), "lib_sha256": lib_hash},
         "episode_return_hist_nonzero": None if hist is None else int((hist > 0).sum().item()),
         "done_on_bounds": bool(args.done_on_bounds),
+        **({"dumped_outputs": dumped} if dumped is not None else {}),
         "nonfinite_envs": int(nf.item()),
         "nonfinite_note": "envs (over all ranks) whose state went non-finite during the run (cp_nonfinite_counts); 0 "
                           "since the coordinate-velocity clamp (btMultiBody m_maxCoordinateVelocity, DESIGN.md §3) "
@@ -1087,10 +1160,10 @@ def main():
                     or args.streams > 1 or args.raster or next_step or args.shape != "auto"
                     or args.reset_shape not in (None, "auto")
                     or args.solver_iterations is not None or args.batch != 65536 or args.repeats != 3)
-    if rank == 0 and world == 1 and headline and not (args.no_secondary or args.no_cpu_baseline):
+    if rank == 0 and world == 1 and args.full and headline and not (args.no_secondary or args.no_cpu_baseline):
         log("secondary configurations ...")
         out["secondary"] = secondary_lines(dev, R)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log("cpu baseline ...")
         out["cpu_baseline"] = cpu_baseline(R, args.cpu_seconds)
         out["gym_mirror_b1_gpu"] = gym_mirror_rate()   # a GPU B = 1 measurement, beside (not in) cpu_baseline

@@ -52,6 +52,26 @@ def test_workload_names():
     assert "4,096" in s and "continuous" in s and "configs[1]" in s
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: float32 .npy files, whole while they fit the byte budget, else the same seeded
+    sample of flat indices on every call; never more bytes than the budget."""
+    outs = {"obs": torch.arange(6000, dtype=torch.float32).view(100, 3, 2, 10),
+            "done": (torch.arange(100) % 3 == 0).to(torch.uint8),
+            "pixels": torch.arange(50000).to(torch.float16).view(100, 500)}
+    wrote = bench.dump_outputs(outs, str(tmp_path / "a"), max_bytes=100000)
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in outs}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert np.array_equal(a["obs"], outs["obs"].numpy()) and np.array_equal(a["done"], outs["done"].numpy())
+    assert "of" not in wrote["obs"] and wrote["pixels"]["of"] == [100, 500]
+    assert sum(v.nbytes for v in a.values()) <= 100000 and a["pixels"].size == (100000 - 24400) // 4
+    # the sample: sorted flat indices of the full array, equal from call to call
+    flat = outs["pixels"].to(torch.float32).reshape(-1).numpy()
+    assert np.all(np.isin(a["pixels"], flat)) and np.all(np.diff(a["pixels"]) >= 0) and len(set(a["pixels"])) > 1000
+    bench.dump_outputs(outs, str(tmp_path / "b"), max_bytes=100000)
+    assert np.array_equal(np.load(tmp_path / "b" / "pixels.npy"), a["pixels"])
+    assert bench.DUMP_MAX_BYTES <= 64_000_000
+
+
 def test_step_kernel_bytes_formula():
     # DESIGN.md §5: 1,059 B per env-step at R = 3 with discrete actions
     assert bench.step_kernel_bytes(3, 2) == 1059

@@ -1,4 +1,4 @@
-"""The default bench line's C3_rollout_k200 secondary leg alone (bench.secondary_lines), repeated:
+"""The `bench.py --full` line's C3_rollout_k200 secondary leg alone (bench.secondary_lines), repeated:
     python tools/rollout_leg.py [reps]        (CP_LIB_PATH selects the library)
 Prints one JSON line per repetition."""
 import json

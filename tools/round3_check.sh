@@ -6,8 +6,9 @@ set -u
 TAG=${1:-rd3f}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/gpurun_out
-timeout -k 10 900 python -u bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { echo "bench rc=$?"; tail -5 gpurun_out/bench_$TAG.err; exit 1; }
-tail -c 600 gpurun_out/bench_$TAG.json; echo
+O=${BENCH_OUT:-$R/bench_out}; mkdir -p $O
+timeout -k 10 900 python -u bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.err || { echo "bench rc=$?"; tail -5 $O/bench_$TAG.err; exit 1; }
+tail -c 600 $O/bench_$TAG.json; echo
 timeout -k 10 300 python -u bench.py --rollout 1 --no-cpu-baseline > gpurun_out/bench_${TAG}_roll1.json 2> gpurun_out/bench_${TAG}_roll1.err || exit 1
 bash tools/profile.sh $TAG || exit 1
 python tools/summarize_profile.py $TAG || exit 1

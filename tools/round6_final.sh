@@ -13,8 +13,8 @@ if [ "${PART:-1}" = 1 ]; then
   tail -1 "$O/${TAG}_smoke.log"
   bash tools/profile.sh "$TAG" || exit 1
 else
-  timeout -k 10 900 python bench.py > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" || { tail -5 "$O/${TAG}_bench.err"; exit 1; }
-  timeout -k 10 600 python bench.py --steps 20 --warmup 5 > "$O/${TAG}_bench20.json" 2> "$O/${TAG}_bench20.err" \
+  timeout -k 10 900 python bench.py --full > "$O/${TAG}_bench.json" 2> "$O/${TAG}_bench.err" || { tail -5 "$O/${TAG}_bench.err"; exit 1; }
+  timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > "$O/${TAG}_bench20.json" 2> "$O/${TAG}_bench20.err" \
       || { tail -5 "$O/${TAG}_bench20.err"; exit 1; }
   echo "benches done"
 fi
