@@ -5,7 +5,7 @@ library's entry points with these types.
 """
 import ctypes as C
 
-CP_ABI_VERSION = 6
+CP_ABI_VERSION = 7
 
 CP_BODY_GROUND, CP_BODY_CART, CP_BODY_POLE, CP_BODY_CART2, CP_BODY_POLE2 = range(5)
 CP_NUM_BODIES = 5
@@ -163,6 +163,24 @@ class cp_raster_config(C.Structure):
         ("diffuse", C.c_float),
         ("background", _F3),
         ("color", _F3 * CP_NUM_BODIES),
+    ]
+
+
+# ---- in-kernel MLP policy (include/cartpole_amd.h: cp_policy)
+CP_POLICY_MAX_LAYERS = 4
+CP_POLICY_MAX_WIDTH = 128
+CP_HEAD_TANH, CP_HEAD_CLIP, CP_HEAD_ARGMAX, CP_HEAD_SAMPLE = range(4)
+HEADS = {"tanh": CP_HEAD_TANH, "clip": CP_HEAD_CLIP, "argmax": CP_HEAD_ARGMAX, "sample": CP_HEAD_SAMPLE}
+
+
+class cp_policy(C.Structure):
+    _fields_ = [
+        ("num_layers", C.c_int32),
+        ("width", C.c_int32 * (CP_POLICY_MAX_LAYERS + 1)),
+        ("head", C.c_int32),
+        ("epsilon", C.c_float),
+        ("seed", C.c_uint64),
+        ("weights", C.c_void_p),
     ]
 
 

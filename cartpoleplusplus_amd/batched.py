@@ -104,6 +104,7 @@ class BatchedCartpole:
         self.terminal_obs = torch.zeros_like(self.obs) if config.autoreset else None
         self.readback = None
         self.pixels = None
+        self.policy = self.policy_weights = None   # set_policy
 
     # -------------------------------------------------------------- plumbing
     def _stream(self):
@@ -278,6 +279,40 @@ class BatchedCartpole:
         self.state8 = torch.zeros((self.B, self.R, self.S, 2, 8), device=self.device) if state8 else None
         native.check(self.h, self.lib.cp_set_lqr(self.h, _ptr(g), int(bool(per_env)), _ptr(self.state8),
                                                  float(done_pos), float(done_angle)), "cp_set_lqr")
+
+    # ------------------------------------------------- in-kernel MLP policy
+    def set_policy(self, layers, head="tanh", epsilon=0.0, seed=0):
+        """Dense ReLU MLP policy for policy_act() (cp_set_policy): layers is a list of
+        (W, b) tensors or an nn.Sequential of Linear / ReLU, head "tanh" / "clip" (continuous, 4 outputs)
+        or "argmax" / "sample" (discrete, 2 x 5 logits; epsilon, seed for "sample").  None turns it off.
+        self.policy_weights is the packed device tensor the kernels read at every launch: new weights
+        written into it in place (policy.repack) take effect at the next launch."""
+        from . import policy
+        if layers is None:
+            native.check(self.h, self.lib.cp_set_policy(self.h, None), "cp_set_policy")
+            self.policy_weights = self.policy = None
+            return None
+        packed, pol = policy.pack(layers, head, epsilon=epsilon, seed=seed, device=self.device)
+        native.check(self.h, self.lib.cp_set_policy(self.h, C.byref(pol)), "cp_set_policy")
+        self.policy_weights, self.policy = packed, pol
+        return packed
+
+    def _policy_kind(self):
+        if self.policy is None:
+            raise native.CartpoleError("no policy set (set_policy)")
+        return self.policy.head in (abi.CP_HEAD_ARGMAX, abi.CP_HEAD_SAMPLE)
+
+    def policy_act(self, obs=None, noise=None):
+        """The policy's actions (B,2,2) float32 or (B,2) int8 for obs (default: self.obs) and the envs'
+        counters (cp_policy_act); noise (B,2,2) is added before the clip of a continuous head.  Pass the
+        result to step()."""
+        discrete = self._policy_kind()
+        o = _device_buffer(self.obs if obs is None else obs, (self.B, self.R, 2, 7), torch.float32, self.device, "obs")
+        n = None if noise is None else _device_buffer(noise, (self.B, 2, 2), torch.float32, self.device, "noise")
+        a = torch.empty((self.B, 2) if discrete else (self.B, 2, 2), device=self.device,
+                        dtype=torch.int8 if discrete else torch.float32)
+        native.check(self.h, self.lib.cp_policy_act(self.h, _ptr(o), _ptr(n), _ptr(a), self._stream()), "cp_policy_act")
+        return a
 
     def set_bump_forces(self, forces):
         """Parity mode (bump_mode='host'): LINK-frame bump forces (B, 30, 2, 2).  float64 input goes

@@ -126,6 +126,21 @@ struct Lqr {
     float done_angle;
 };
 
+// in-kernel MLP policy arguments (cp_set_policy, cp_policy.h): the caller's cp_policy fields, the handle's
+// activation scratch and the per-call pointers
+struct Pol {
+    int32_t num_layers;
+    int32_t width[CP_POLICY_MAX_LAYERS + 1];
+    int32_t head;
+    float epsilon;
+    uint64_t seed;
+    const float* weights;  // packed layers, W[out][in] then b[out] each
+    float* scratch;        // [2][CP_POLICY_MAX_WIDTH][B] lane-private ping-pong activations
+    const float* obs_in;   // [B][R][2][7] the obs to act on
+    const float* noise;    // [B][2][2] or null
+    void* actions_out;     // [B][2][2] f32 or [B][2] i8
+};
+
 // Per-handle device buffers.  `state` and `scratch` hold the handle's real type.
 struct Bufs {
     void* state;       // [CP_STATE_FIELDS][B] real
@@ -176,3 +191,7 @@ struct Bufs {
     }
 CP_DECLARE_LAUNCHES(cp)
 CP_DECLARE_LAUNCHES(cp64)
+// the MLP policy's kernels exist in fp32 only (cp_kernels.hip defines CP_POLICY)
+namespace cp {
+void launch_policy_act(int kind, const cp_config& cfg, const cpc::Bufs& b, const cpc::Pol& pol, hipStream_t st);
+}

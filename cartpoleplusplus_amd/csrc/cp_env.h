@@ -652,6 +652,9 @@ enum : uint32_t { RF_DONE = 1u, RF_RESETTING = 2u, RF_LAST_SIM = 4u, RF_LQR_DONE
 static_assert(RC_END - RC_K == CP_SCR_RC_FIELDS, "rollout state rows of the scratch SoA (cp_common.h)");
 static_assert(RC_K >= CP_SCR_HDR_FIELDS, "rollout state must not overlap the CP_HDR_SCRATCH manifold headers");
 
+// the MLP policy's device function and its stand-alone kernel (cp_policy_act; fp32)
+#include "cp_policy.h"
+
 template <int KIND, bool LQR, bool LAT, bool PM = false, bool SLP = false>
 __global__ void __launch_bounds__(WAVE)
 __attribute__((amdgpu_waves_per_eu(LAT ? 1 : CP_WAVES_PER_EU, LAT ? 1 : CP_WAVES_PER_EU)))
@@ -1018,6 +1021,16 @@ void launch_rollout(bool lat, int kind, const cp_config& cfg, const Bufs& b, int
                                                          term_out, lq, st);
     }
 }
+
+#ifdef CP_POLICY  // the fp32 translation unit only
+void launch_policy_act(int kind, const cp_config& cfg, const Bufs& b, const cpc::Pol& pol, hipStream_t st) {
+    const dim3 grid(env_grid(cfg.num_envs, WAVE)), block(WAVE);  // one lane per env
+    if (kind == CP_ACTION_CONTINUOUS)
+        hipLaunchKernelGGL(cp_policy_act_kernel<CP_ACTION_CONTINUOUS>, grid, block, 0, st, cfg, b, pol);
+    else
+        hipLaunchKernelGGL(cp_policy_act_kernel<CP_ACTION_DISCRETE>, grid, block, 0, st, cfg, b, pol);
+}
+#endif  // CP_POLICY
 
 void launch_step(int lat, int kind, const cp_config& cfg, const Bufs& b, const void* actions, float* obs_out,
                  float* reward_out, uint8_t* done_out, float* term_out, float* readback, int rb_bug, const Lqr& lq,

@@ -25,11 +25,13 @@
 
 #define CP_NS cp
 #define CP_REAL float
+#define CP_POLICY  // the MLP policy's kernels and launchers (cp_policy.h): fp32 only
 #include "cp_math.h"
 #include "cp_physics.h"
 #include "cp_env.h"
 #undef CP_NS
 #undef CP_REAL
+#undef CP_POLICY
 
 #include "cp_raster.h"
 #include "cp_replay.h"
@@ -157,6 +159,8 @@ struct cp_handle {
     float* readback;
     int readback_bug;
     cpc::Lqr lqr;
+    cpc::Pol pol;      // the MLP policy (cp_set_policy): the caller's fields and the handle's scratch
+    bool pol_on;
     cp_timing timing;
     cp_raster_config raster;
     uint16_t* pixels;  // raster obs output (NULL: raster off)
@@ -360,6 +364,8 @@ int cp_create(const cp_config* cfg, int device, cp_handle** out) {
     h->readback_bug = 1;
     h->lqr = cpc::Lqr{nullptr, 0, nullptr, 0.0f, 0.0f};
     h->f64 = cfg->precision == CP_PRECISION_F64;
+    std::memset(&h->pol, 0, sizeof(h->pol));
+    h->pol_on = false;
     h->pixels = nullptr;
     {
         const char* v1 = std::getenv("CP_RENDER_V1");
@@ -471,6 +477,7 @@ void cp_destroy(cp_handle* h) {
     (void)hipFree(h->b.list);
     (void)hipFree(h->count2);
     (void)hipFree(h->b.scratch);
+    (void)hipFree(h->pol.scratch);
     (void)hipFree(h->b.stamps);
     (void)hipFree(h->b.stepped);
     (void)hipFree(h->b.pman);
@@ -758,6 +765,80 @@ int cp_rollout(cp_handle* h, int steps, const void* actions, int action_kind, fl
     return 0;
 }
 
+// the checks of a cp_policy that need no handle; returns its number of weight floats, or -1 with the cause
+static int64_t policy_floats(cp_handle* h, const cp_policy* p, const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (!p) return fail(h, w + "null policy");
+    if (p->num_layers < 1 || p->num_layers > CP_POLICY_MAX_LAYERS)
+        return fail(h, w + "num_layers must be in 1.." + std::to_string(CP_POLICY_MAX_LAYERS));
+    for (int l = 0; l <= p->num_layers; ++l)
+        if (p->width[l] < 1 || p->width[l] > CP_POLICY_MAX_WIDTH)
+            return fail(h, w + "width[" + std::to_string(l) + "] must be in 1.." + std::to_string(CP_POLICY_MAX_WIDTH));
+    if (p->head < CP_HEAD_TANH || p->head > CP_HEAD_SAMPLE)
+        return fail(h, w + "head must be CP_HEAD_TANH, _CLIP, _ARGMAX or _SAMPLE");
+    const int out = (p->head == CP_HEAD_TANH || p->head == CP_HEAD_CLIP) ? 4 : 2 * CP_NUM_DISCRETE;
+    if (p->width[p->num_layers] != out)
+        return fail(h, w + "the head's out width must be " + std::to_string(out) +
+                           (out == 4 ? " (continuous: a00 a01 a10 a11)" : " (discrete: 2 carts x 5 logits)"));
+    if (!(p->epsilon >= 0.0f && p->epsilon <= 1.0f)) return fail(h, w + "epsilon must be in [0, 1]");
+    int64_t n = 0;
+    for (int l = 0; l < p->num_layers; ++l) n += (int64_t)p->width[l + 1] * (p->width[l] + 1);
+    return n;
+}
+
+int64_t cp_policy_floats(const cp_policy* p) { return policy_floats(nullptr, p, "cp_policy_floats"); }
+
+int cp_set_policy(cp_handle* h, const cp_policy* p) {
+    if (!h) return fail(h, "cp_set_policy: null handle");
+    if (!p) {
+        h->pol_on = false;
+        return 0;
+    }
+    if (policy_floats(h, p, "cp_set_policy") < 0) return -1;
+    if (h->f64) return fail(h, "cp_set_policy: the MLP policy is fp32 only (not for CP_PRECISION_F64 handles)");
+    if (h->cfg.phys.model_flags & (CP_MODEL_PERSISTENT | CP_MODEL_SLEEPING))
+        return fail(h, "cp_set_policy: not built for CP_MODEL_PERSISTENT / CP_MODEL_SLEEPING handles");
+    if (h->cfg.autoreset == CP_AUTORESET_NEXT_STEP)
+        return fail(h, "cp_set_policy: not for CP_AUTORESET_NEXT_STEP handles (a finished env's next action is ignored)");
+    if (h->lqr.gains) return fail(h, "cp_set_policy: the handle has the LQR policy on (cp_set_lqr); turn it off first");
+    if (p->width[0] != 14 * h->cfg.action_repeats)
+        return fail(h, "cp_set_policy: width[0] must be 14 * action_repeats = " + std::to_string(14 * h->cfg.action_repeats) +
+                           " (the obs [R][2][7] flattened)");
+    if (!p->weights) return fail(h, "cp_set_policy: null weights");
+    if ((unsigned long long)h->cfg.num_envs * 2ull * CP_POLICY_MAX_WIDTH * sizeof(float) >= (1ull << 32))
+        return fail(h, "cp_set_policy: num_envs too large (the activation scratch SoA must stay below 4 GiB)");
+    if (!h->pol.scratch) {
+        CP_TRY(h, hipSetDevice(h->device));
+        CP_TRY(h, hipMalloc((void**)&h->pol.scratch, (size_t)2 * CP_POLICY_MAX_WIDTH * h->cfg.num_envs * sizeof(float)));
+    }
+    h->pol.num_layers = p->num_layers;
+    for (int l = 0; l <= CP_POLICY_MAX_LAYERS; ++l) h->pol.width[l] = l <= p->num_layers ? p->width[l] : 0;
+    h->pol.head = p->head;
+    h->pol.epsilon = p->epsilon;
+    h->pol.seed = p->seed;
+    h->pol.weights = p->weights;
+    h->pol_on = true;
+    return 0;
+}
+
+static int policy_kind(const cp_handle* h) {
+    return (h->pol.head == CP_HEAD_TANH || h->pol.head == CP_HEAD_CLIP) ? CP_ACTION_CONTINUOUS : CP_ACTION_DISCRETE;
+}
+
+int cp_policy_act(cp_handle* h, const float* obs, const float* noise, void* actions_out, void* stream) {
+    if (!h || !obs || !actions_out) return fail(h, "cp_policy_act: null argument");
+    if (!h->pol_on) return fail(h, "cp_policy_act: no policy set (cp_set_policy)");
+    hipStream_t st = (hipStream_t)stream;
+    CP_TRY(h, hipSetDevice(h->device));
+    cpc::Pol pol = h->pol;
+    pol.obs_in = obs;
+    pol.noise = noise;
+    pol.actions_out = actions_out;
+    cp::launch_policy_act(policy_kind(h), h->cfg, h->b, pol, st);
+    CP_TRY(h, hipGetLastError());
+    return 0;
+}
+
 int cp_set_readback(cp_handle* h, float* readback_out, int reference_bug) {
     if (!h) return fail(h, "cp_set_readback: null handle");
     h->readback = readback_out;
@@ -771,6 +852,8 @@ int cp_set_lqr(cp_handle* h, const float* gains, int per_env, float* state8_out,
     if (!gains && state8_out) return fail(h, "cp_set_lqr: the 8-state readback needs the LQR policy on");
     if (gains && (h->cfg.phys.model_flags & CP_MODEL_SLEEPING))
         return fail(h, "cp_set_lqr: the LQR policy is not built for CP_MODEL_SLEEPING handles (oracle-only)");
+    if (gains && h->pol_on)
+        return fail(h, "cp_set_lqr: the handle has an MLP policy on (cp_set_policy); turn it off first");
     h->lqr.gains = gains;
     h->lqr.per_env = per_env ? 1 : 0;
     h->lqr.state8 = state8_out;

@@ -23,6 +23,7 @@ EXPORTS = (
     "cp_set_lqr", "cp_get_stepped", "cp_replay_init", "cp_replay_add", "cp_replay_sample",
     "cp_state_bytes", "cp_set_kernel_shape", "cp_get_kernel_shape", "cp_rollout",
     "cp_nonfinite_counts", "cp_render_kernel_name",
+    "cp_policy_floats", "cp_set_policy", "cp_policy_act",
 )
 
 _lib = None
@@ -82,6 +83,9 @@ def load():
         "cp_rollout": (I, [VP, I, VP, I, VP, VP, VP, VP, VP]),
         "cp_set_kernel_shape": (I, [VP, I, I]),
         "cp_get_kernel_shape": (I, [VP, P(I), P(I)]),
+        "cp_policy_floats": (C.c_int64, [P(abi.cp_policy)]),
+        "cp_set_policy": (I, [VP, P(abi.cp_policy)]),
+        "cp_policy_act": (I, [VP, VP, VP, VP, VP]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

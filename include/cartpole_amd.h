@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define CP_ABI_VERSION 6
+#define CP_ABI_VERSION 7
 
 /* Bodies, in the reference's loadURDF order (bullet_cartpole.py:154-160). */
 #define CP_BODY_GROUND 0
@@ -265,6 +265,59 @@ int cp_step(cp_handle* h, const void* actions, int action_kind,
  * launch is timed as one step-kernel launch. */
 int cp_rollout(cp_handle* h, int steps, const void* actions, int action_kind, float* obs_out,
                float* reward_out, uint8_t* done_out, float* terminal_obs_out, void* stream);
+
+/* ---- In-kernel MLP policy (the agents' observation -> small MLP -> action -> step loop:
+ * lrpg_cartpole.py:149-163, ddpg_cartpole.py:121-138, naf_cartpole.py) ----------
+ * A dense ReLU MLP evaluated per env by cp_policy_act's kernel for the per-step path.  Inference only; fp32.
+ *
+ * Weights: the layers packed one after another, per layer W[out][in] row-major, then b[out]
+ * (cp_policy_floats floats in all).  The library never copies them: they are read from the caller's
+ * device buffer at every launch, so an optimiser step written into it takes effect at the next launch.
+ *
+ * Arithmetic (all fp32; the order is part of the contract).  x = the env's obs [R][2][7] flattened,
+ * unscaled.  Dense layer: acc = b[j], then acc = fmaf(W[j][i], x[i], acc) for i = 0 .. in-1 ascending;
+ * hidden units acc > 0 ? acc : 0; the last layer is linear (z).  With n the caller's noise (0 when NULL):
+ *   CLIP    a = min(max(z + n, -1), 1)
+ *   TANH    a = min(max(tanhf(z) + n, -1), 1)
+ *   ARGMAX  per cart the lowest index among its maximal logits
+ *   SAMPLE  per cart c: (w0..w3) = Philox4x32-10(ctr = (0x40000000 + 2*steps + c, episode, gid_lo, gid_hi),
+ *           key = seed), steps / episode the env's counters before the step, gid = env_id_offset + i;
+ *           u_k = (w_k >> 8) * 2^-24; if u0 < epsilon: a = ((w1 >> 8) * 5) >> 24; else m = max z,
+ *           e_j = expf(z_j - m), S = e_0 + .. + e_4 in order, a = the smallest index whose running sum
+ *           exceeds u2 * S (4 if none does).
+ * An env that is done before a step (no autoreset) is not evaluated; its actions_out entry is 0. */
+#define CP_POLICY_MAX_LAYERS 4      /* dense layers incl. the output layer (ddpg's 100,100,50 + head) */
+#define CP_POLICY_MAX_WIDTH  128    /* widest layer, input included (14*R <= 128) */
+#define CP_HEAD_TANH   0  /* continuous, out width 4 (a00 a01 a10 a11): the ddpg/naf actor head */
+#define CP_HEAD_CLIP   1  /* continuous, linear head clipped to [-1,1] */
+#define CP_HEAD_ARGMAX 2  /* discrete, out width 10 = 2 carts x 5 logits: lrpg eval (tf.argmax) */
+#define CP_HEAD_SAMPLE 3  /* discrete: lrpg's epsilon-greedy multinomial (lrpg_cartpole.py:132-146) */
+typedef struct cp_policy {
+    int32_t num_layers;                       /* 1..CP_POLICY_MAX_LAYERS */
+    int32_t width[CP_POLICY_MAX_LAYERS + 1];  /* width[0] = 14*R, width[num_layers] = 4 or 10 */
+    int32_t head;
+    float   epsilon;                          /* SAMPLE only, in [0,1] */
+    uint64_t seed;                            /* SAMPLE only: Philox key */
+    const float* weights;                     /* device, caller-owned, read at every launch */
+} cp_policy;
+
+/* Number of weight floats of `p`: the sum of out * (in + 1) over its layers.  Applies the checks that need
+ * no handle (layer count, widths, head / out width, epsilon); < 0 and cp_last_error(NULL) if invalid.
+ * No GPU. */
+int64_t cp_policy_floats(const cp_policy* p);
+
+/* Turn the policy on (a copy of *p; the weights stay the caller's) or off (NULL).  Rejected, with the
+ * cause in cp_last_error: fp64 handles, CP_MODEL_PERSISTENT / CP_MODEL_SLEEPING handles,
+ * CP_AUTORESET_NEXT_STEP handles, a handle with the LQR policy on (and cp_set_lqr rejects a handle with
+ * a policy on), width[0] != 14*R, and whatever cp_policy_floats rejects.  Allocates the handle's
+ * activation scratch (2 * CP_POLICY_MAX_WIDTH floats per env) on first use.  cp_step and cp_rollout are
+ * unaffected by a policy. */
+int cp_set_policy(cp_handle* h, const cp_policy* p);
+
+/* The policy's actions for every env from obs [B][R][2][7] (the obs the caller last received), noise
+ * ([B][2][2], may be NULL; continuous heads) and the state's counters: actions_out [B][2][2] f32
+ * (TANH, CLIP) or [B][2] i8 (ARGMAX, SAMPLE), which the caller then passes to cp_step. */
+int cp_policy_act(cp_handle* h, const float* obs, const float* noise, void* actions_out, void* stream);
 
 /* Optional per-substep 12-state readback of both poles (bullet_cartpole.py:212-234,
  * exposed there as monkey_positions / monkey_velocities):

@@ -4,7 +4,13 @@
     ingest  env.step + ReplayMemory.after_step (f3; 2^22-event ring, 42-float states)
     sample  ReplayMemory.sample(n) alone (device gather)
 Timed with HIP events on torch's current stream (all launches go there).  Prints one
-JSON line; per-event / per-sample algorithmic bytes as in DESIGN.md §Replay memory."""
+JSON line; per-event / per-sample algorithmic bytes as in DESIGN.md §Replay memory.
+
+--policy: the in-kernel MLP policy instead, one session, K = --steps env-steps per run,
+one warm-up run and the median of --repeats runs each:
+    rollout         cp_rollout with precomputed actions (the yardstick)
+    act_loop        K x (cp_policy_act + cp_step), "100,50" MLP with the SAMPLE head
+    torch_loop      what a user does without it: K x (torch MLP forward + torch.multinomial + cp_step)"""
 import argparse
 import json
 import os
@@ -29,13 +35,60 @@ def timed(fn, steps):
     return e0.elapsed_time(e1) / steps
 
 
+def policy_bench(args):
+    import statistics
+    B, K, R = args.batch, args.steps, 3
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(1234)
+    acts = torch.randint(0, 5, (K, B, 2), dtype=torch.int8, device=dev, generator=g)
+    mlp = torch.nn.Sequential(torch.nn.Linear(14 * R, 100), torch.nn.ReLU(), torch.nn.Linear(100, 50), torch.nn.ReLU(),
+                              torch.nn.Linear(50, 10)).to(dev)
+    env = BatchedCartpole(B, 0, action_repeats=R, initial_force=55.0, autoreset=True, seed=1234)
+    env.set_policy(mlp, "sample", epsilon=0.05, seed=7)
+    env.reserve_rollout(K, terminal=False)
+    env.reset()
+
+    def run(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    def torch_loop():
+        with torch.no_grad():
+            for _ in range(K):
+                logits = mlp(env.obs.view(B, -1)).view(B * 2, 5)
+                a = torch.multinomial(torch.softmax(logits, 1), 1).view(B, 2).to(torch.int8)
+                env.step(a)
+
+    legs = {"rollout": lambda: env.rollout(acts, terminal=False),
+            "act_loop": lambda: [env.step(env.policy_act()) for _ in range(K)],
+            "torch_loop": torch_loop}
+    out = {"batch": B, "steps": K, "repeats": args.repeats, "policy": "42-100-50-10 sample"}
+    for name, fn in legs.items():
+        run(fn)  # warm-up
+        ms = [run(fn) for _ in range(args.repeats)]
+        out[name + "_ms"] = ms
+        out[name + "_env_steps_per_s"] = B * K / (statistics.median(ms) * 1e-3)
+    out["act_loop_over_rollout"] = out["act_loop_env_steps_per_s"] / out["rollout_env_steps_per_s"]
+    out["act_loop_over_torch_loop"] = out["act_loop_env_steps_per_s"] / out["torch_loop_env_steps_per_s"]
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--policy", action="store_true")
+    ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--ring", type=int, default=1 << 22)
     ap.add_argument("--sample", type=int, default=65536)
     args = ap.parse_args()
+    if args.policy:
+        return policy_bench(args)
     B, K, R = args.batch, args.steps, 3
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(1234)

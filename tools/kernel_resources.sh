@@ -1,5 +1,5 @@
 #!/bin/bash
-# Registers, spills and scratch of every kernel in the built library, read from the embedded gfx950
+# Registers (VGPR / AGPR / SGPR), spills, scratch and LDS of every kernel in the built library, read from the embedded gfx950
 # code objects (one bundle per translation unit; no recompile):
 #   bash tools/kernel_resources.sh [lib.so] [name regex]
 LIB=${1:-$(dirname $0)/../cartpoleplusplus_amd/libcartpole_hip.so}
@@ -19,7 +19,7 @@ PY
 for f in $T/bundle*.bin; do
   /opt/rocm/lib/llvm/bin/clang-offload-bundler --unbundle --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 \
       --input=$f --output=$f.elf 2>/dev/null || continue
-  /opt/rocm/lib/llvm/bin/llvm-readelf --notes $f.elf | grep -E "\.name:|\.vgpr_count|\.private_segment_fixed_size|\.sgpr_spill|\.vgpr_spill" \
-      | paste - - - - - | grep -E "$PAT" | sed 's/  */ /g; s/ \.name: / /; s/\.private_segment_fixed_size/scratch/; s/\.sgpr_spill_count/sgpr_spill/; s/\.vgpr_count/vgpr/; s/\.vgpr_spill_count/vgpr_spill/'
+  /opt/rocm/lib/llvm/bin/llvm-readelf --notes $f.elf | grep -E "\.name:|\.vgpr_count|\.agpr_count|\.sgpr_count|\.group_segment_fixed_size|\.private_segment_fixed_size|\.sgpr_spill|\.vgpr_spill" \
+      | paste - - - - - - - - | grep -E "$PAT" | sed 's/  */ /g; s/ \.name: / /; s/\.private_segment_fixed_size/scratch/; s/\.group_segment_fixed_size/lds/; s/\.sgpr_spill_count/sgpr_spill/; s/\.sgpr_count/sgpr/; s/\.agpr_count/agpr/; s/\.vgpr_count/vgpr/; s/\.vgpr_spill_count/vgpr_spill/'
 done
 rm -rf $T
