@@ -11,7 +11,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/cartpole_amd.h"
+#include "cp_shapes.h"
 
 #define CP_DEV __device__ __forceinline__
 
@@ -185,7 +188,7 @@ struct Bufs {
     void launch_step(int shape, int kind, const cp_config& cfg, const cpc::Bufs& b, const void* actions,         \
                      float* obs_out, float* reward_out, uint8_t* done_out, float* term_out, float* readback,    \
                      int rb_bug, const cpc::Lqr& lq, hipStream_t st);                                            \
-    void launch_rollout(bool lat, int kind, const cp_config& cfg, const cpc::Bufs& b, int steps,                 \
+    void launch_rollout(int shape, int kind, const cp_config& cfg, const cpc::Bufs& b, int steps,                \
                         const void* actions, float* obs_out, float* reward_out, uint8_t* done_out,              \
                         float* term_out, const cpc::Lqr& lq, hipStream_t st);                                   \
     }

@@ -899,127 +899,100 @@ void launch_nextstep_resolve(const cp_config& cfg, const Bufs& b, const uint8_t*
                        nobs, obs_out);
 }
 
-// shape: 0 throughput, 1 latency, 2 latency on the WIDE layout (cp_set_kernel_shape; fp32 default model only)
+template <bool V> using Bool = std::integral_constant<bool, V>;
+template <int V> using Int = std::integral_constant<int, V>;
+using Yes = Bool<true>;
+using No = Bool<false>;
+
+// The one map from a launch's run-time inputs to the kernels' template switches: f(LAT, PM, SLP, WIDE) is called
+// once, with std::integral_constants, for the variant that serves (model_flags, shape).  MAXW is the widest layout
+// the kernel is built on (64 reset, 16 step, 0 rollout: two lanes only), Q its LQR switch (no LQR policy on the
+// sleeping model: cp_set_lqr rejects it).  The variants named here are the ones that get built: fp64 and the
+// two models have the two-lane latency variant only (cps::latency_only).
+template <int MAXW, bool Q, typename F>
+static void with_layout(unsigned model_flags, int shape, F f) {
+    if (model_flags & CP_MODEL_PERSISTENT) return f(Yes{}, Yes{}, No{}, Int<0>{});
+    if constexpr (!Q) {
+        if (model_flags & CP_MODEL_SLEEPING) return f(Yes{}, No{}, Yes{}, Int<0>{});
+    }
+    if constexpr (!kF64 && MAXW >= 16) {
+        const int lanes = cps::lanes_per_env(shape);
+        if constexpr (MAXW >= 64) {
+            if (lanes == 64) return f(Yes{}, No{}, No{}, Int<64>{});
+        }
+        if (lanes == 16) return f(Yes{}, No{}, No{}, Int<16>{});
+        if (lanes == 8) return f(Yes{}, No{}, No{}, Int<8>{});
+    }
+    // the fp64 unit has always built cp_rollout_kernel's throughput variants, which nothing there launches: the
+    // arm is compiled for them too, so that unit's device code stays what it was
+    if constexpr (!kF64 || MAXW == 0) {
+        if (!kF64 && shape == CP_SHAPE_THROUGHPUT) return f(No{}, No{}, No{}, Int<0>{});
+    }
+    f(Yes{}, No{}, No{}, Int<0>{});
+}
+
+// with_layout behind the action kind and the LQR switch: f(KIND, LQR, LAT, PM, SLP, WIDE)
+template <int MAXW, typename F>
+static void with_variant(unsigned model_flags, int shape, int kind, bool lqr, F f) {
+    auto go = [&](auto k, auto q) {
+        with_layout<MAXW, decltype(q)::value>(model_flags, shape, [&](auto... sw) { f(k, q, sw...); });
+    };
+    using C = Int<CP_ACTION_CONTINUOUS>;
+    using D = Int<CP_ACTION_DISCRETE>;
+    if (kind == CP_ACTION_CONTINUOUS) lqr ? go(C{}, Yes{}) : go(C{}, No{});
+    else lqr ? go(D{}, Yes{}) : go(D{}, No{});
+}
+
+// WAVE-sized blocks for `envs` envs on a WIDE-lane layout (0: the two-lane layout)
+static inline dim3 layout_grid(int wide, int envs) { return dim3(env_grid((wide ? wide : 2) * envs, WAVE)); }
+
 void launch_reset(int shape, const cp_config& cfg, const Bufs& b, float* obs_out, hipStream_t st) {
-    const bool lat = shape != 0;
-    const int wide = (kF64 || (cfg.phys.model_flags & (CP_MODEL_PERSISTENT | CP_MODEL_SLEEPING))) ? 0
-                     : shape == CP_SHAPE_WIDE ? 16 : shape == CP_SHAPE_WIDE8 ? 8 : shape == CP_SHAPE_WIDE64 ? 64 : 0;
-    const dim3 grid(env_grid((wide ? wide : 2) * cfg.num_envs, WAVE)), block(WAVE);  // lanes per env
-    if (cfg.phys.model_flags & CP_MODEL_PERSISTENT) {  // the persistent-manifold model: latency shape only
-        hipLaunchKernelGGL((cp_reset_kernel<true, true>), grid, block, 0, st, cfg, b, obs_out);
-        return;
-    }
-    if (cfg.phys.model_flags & CP_MODEL_SLEEPING) {  // the sleeping model: latency shape only
-        hipLaunchKernelGGL((cp_reset_kernel<true, false, true>), grid, block, 0, st, cfg, b, obs_out);
-        return;
-    }
-    if constexpr (kF64) {
-        (void)lat;
-        hipLaunchKernelGGL(cp_reset_kernel<true>, grid, block, 0, st, cfg, b, obs_out);
-    } else if (shape == CP_SHAPE_LIST) {
+    auto launch = [&](auto lat, auto pm, auto slp, auto wide, const Bufs& bb, int envs) {
+        hipLaunchKernelGGL((cp_reset_kernel<lat.value, pm.value, slp.value, wide.value>), layout_grid(wide.value, envs),
+                           dim3(WAVE), 0, st, cfg, bb, obs_out);
+    };
+    if (shape == CP_SHAPE_LIST && !cps::latency_only(kF64, cfg.phys.model_flags)) {
         // a launch per layout, each with the grid of its largest list and the range of list lengths it serves;
-        // the others' waves read the length and exit (the tiers of wide_reset_shape_for by the list's length)
+        // the others' waves read the length and exit (the tiers of cps::reset_layout_for by the list's length)
         const int B = cfg.num_envs;
         Bufs bt = b;
-#define CP_LIST_TIER(KERN, LANES, LO, HI)                                                                \
-        if (B > (LO)) {                                                                                   \
-            bt.nlo = (LO);                                                                                \
-            bt.nhi = (HI);                                                                                \
-            const int cap = ((HI) > 0 && B > (HI)) ? (HI) : B;                                            \
-            hipLaunchKernelGGL(KERN, dim3(env_grid((LANES) * cap, WAVE)), block, 0, st, cfg, bt, obs_out); \
-        }
-        CP_LIST_TIER((cp_reset_kernel<true, false, false, 64>), 64, 0, 1024)
-        CP_LIST_TIER((cp_reset_kernel<true, false, false, 16>), 16, 1024, 4096)
-        CP_LIST_TIER(cp_reset_kernel<true>, 2, 4096, 32768)
-        CP_LIST_TIER(cp_reset_kernel<false>, 2, 32768, 0)
-#undef CP_LIST_TIER
-    } else {
-        if (wide == 64) hipLaunchKernelGGL((cp_reset_kernel<true, false, false, 64>), grid, block, 0, st, cfg, b, obs_out);
-        else if (wide == 16) hipLaunchKernelGGL((cp_reset_kernel<true, false, false, 16>), grid, block, 0, st, cfg, b, obs_out);
-        else if (wide == 8) hipLaunchKernelGGL((cp_reset_kernel<true, false, false, 8>), grid, block, 0, st, cfg, b, obs_out);
-        else if (lat) hipLaunchKernelGGL(cp_reset_kernel<true>, grid, block, 0, st, cfg, b, obs_out);
-        else hipLaunchKernelGGL(cp_reset_kernel<false>, grid, block, 0, st, cfg, b, obs_out);
-    }
-}
-
-template <int K, bool Q>
-static void launch_step_t(int shape, const cp_config& cfg, const Bufs& b, const void* actions, float* obs_out,
-                          float* reward_out, uint8_t* done_out, float* term_out, float* readback, int rb_bug,
-                          const Lqr& lq, hipStream_t st) {
-    const bool lat = shape != 0;
-    const int wide = (kF64 || (cfg.phys.model_flags & (CP_MODEL_PERSISTENT | CP_MODEL_SLEEPING))) ? 0
-                     : shape == CP_SHAPE_WIDE ? 16 : shape == CP_SHAPE_WIDE8 ? 8 : shape == CP_SHAPE_WIDE64 ? 16 : 0;  // (64 lanes: reset lists only)
-    const dim3 grid(env_grid((wide ? wide : 2) * cfg.num_envs, WAVE)), block(WAVE);  // lanes per env
-    if (cfg.phys.model_flags & CP_MODEL_PERSISTENT) {  // the persistent-manifold model: latency shape only
-        hipLaunchKernelGGL((cp_step_kernel<K, Q, true, true>), grid, block, 0, st, cfg, b, actions, obs_out,
-                           reward_out, done_out, term_out, readback, rb_bug, lq);
+        auto tier = [&](auto lat, auto wide, int lo, int hi) {
+            if constexpr (!kF64) {  // inside the generic lambda, so that the fp64 unit builds none of the tiers
+                if (B <= lo) return;
+                bt.nlo = lo;
+                bt.nhi = hi;
+                launch(lat, No{}, No{}, wide, bt, (hi > 0 && B > hi) ? hi : B);
+            }
+        };
+        tier(Yes{}, Int<64>{}, 0, 1024);
+        tier(Yes{}, Int<16>{}, 1024, 4096);
+        tier(Yes{}, Int<0>{}, 4096, 32768);
+        tier(No{}, Int<0>{}, 32768, 0);
         return;
     }
-    if constexpr (!Q) {  // the sleeping model: latency shape only, no LQR policy (cp_set_lqr rejects it)
-        if (cfg.phys.model_flags & CP_MODEL_SLEEPING) {
-            hipLaunchKernelGGL((cp_step_kernel<K, false, true, false, true>), grid, block, 0, st, cfg, b, actions,
-                               obs_out, reward_out, done_out, term_out, readback, rb_bug, lq);
-            return;
-        }
-    }
-    if constexpr (kF64) {
-        (void)lat;
-        hipLaunchKernelGGL((cp_step_kernel<K, Q, true>), grid, block, 0, st, cfg, b, actions, obs_out, reward_out,
-                           done_out, term_out, readback, rb_bug, lq);
-    } else {
-        if (wide == 16)
-            hipLaunchKernelGGL((cp_step_kernel<K, Q, true, false, false, 16>), grid, block, 0, st, cfg, b, actions,
-                               obs_out, reward_out, done_out, term_out, readback, rb_bug, lq);
-        else if (wide == 8)
-            hipLaunchKernelGGL((cp_step_kernel<K, Q, true, false, false, 8>), grid, block, 0, st, cfg, b, actions,
-                               obs_out, reward_out, done_out, term_out, readback, rb_bug, lq);
-        else if (lat)
-            hipLaunchKernelGGL((cp_step_kernel<K, Q, true>), grid, block, 0, st, cfg, b, actions, obs_out, reward_out,
-                               done_out, term_out, readback, rb_bug, lq);
-        else
-            hipLaunchKernelGGL((cp_step_kernel<K, Q, false>), grid, block, 0, st, cfg, b, actions, obs_out, reward_out,
-                               done_out, term_out, readback, rb_bug, lq);
-    }
+    with_layout<64, false>(cfg.phys.model_flags, shape, [&](auto... sw) { launch(sw..., b, cfg.num_envs); });
 }
 
-template <int K, bool Q>
-static void launch_rollout_t(bool lat, const cp_config& cfg, const Bufs& b, int steps, const void* actions,
-                             float* obs_out, float* reward_out, uint8_t* done_out, float* term_out, const Lqr& lq,
-                             hipStream_t st) {
-    const dim3 grid(env_grid(2 * cfg.num_envs, WAVE)), block(WAVE);  // two lanes per env
-    if constexpr (!Q) {
-        if (cfg.phys.model_flags & CP_MODEL_SLEEPING) {
-            hipLaunchKernelGGL((cp_rollout_kernel<K, false, true, false, true>), grid, block, 0, st, cfg, b, steps,
-                               actions, obs_out, reward_out, done_out, term_out, lq);
-            return;
-        }
-    }
-    if (cfg.phys.model_flags & CP_MODEL_PERSISTENT)
-        hipLaunchKernelGGL((cp_rollout_kernel<K, Q, true, true>), grid, block, 0, st, cfg, b, steps, actions, obs_out,
-                           reward_out, done_out, term_out, lq);
-    else if (lat || kF64)
-        hipLaunchKernelGGL((cp_rollout_kernel<K, Q, true>), grid, block, 0, st, cfg, b, steps, actions, obs_out,
-                           reward_out, done_out, term_out, lq);
-    else
-        hipLaunchKernelGGL((cp_rollout_kernel<K, Q, false>), grid, block, 0, st, cfg, b, steps, actions, obs_out,
-                           reward_out, done_out, term_out, lq);
+void launch_step(int shape, int kind, const cp_config& cfg, const Bufs& b, const void* actions, float* obs_out,
+                 float* reward_out, uint8_t* done_out, float* term_out, float* readback, int rb_bug, const Lqr& lq,
+                 hipStream_t st) {
+    with_variant<16>(cfg.phys.model_flags, shape, kind, lq.gains != nullptr,
+                     [&](auto k, auto q, auto lat, auto pm, auto slp, auto wide) {
+        hipLaunchKernelGGL((cp_step_kernel<k.value, q.value, lat.value, pm.value, slp.value, wide.value>),
+                           layout_grid(wide.value, cfg.num_envs), dim3(WAVE), 0, st, cfg, b, actions, obs_out,
+                           reward_out, done_out, term_out, readback, rb_bug, lq);
+    });
 }
 
-void launch_rollout(bool lat, int kind, const cp_config& cfg, const Bufs& b, int steps, const void* actions,
+void launch_rollout(int shape, int kind, const cp_config& cfg, const Bufs& b, int steps, const void* actions,
                     float* obs_out, float* reward_out, uint8_t* done_out, float* term_out, const Lqr& lq,
                     hipStream_t st) {
-    const bool q = lq.gains != nullptr;
-    if (kind == CP_ACTION_CONTINUOUS) {
-        if (q) launch_rollout_t<CP_ACTION_CONTINUOUS, true>(lat, cfg, b, steps, actions, obs_out, reward_out, done_out,
-                                                            term_out, lq, st);
-        else launch_rollout_t<CP_ACTION_CONTINUOUS, false>(lat, cfg, b, steps, actions, obs_out, reward_out, done_out,
-                                                           term_out, lq, st);
-    } else {
-        if (q) launch_rollout_t<CP_ACTION_DISCRETE, true>(lat, cfg, b, steps, actions, obs_out, reward_out, done_out,
-                                                          term_out, lq, st);
-        else launch_rollout_t<CP_ACTION_DISCRETE, false>(lat, cfg, b, steps, actions, obs_out, reward_out, done_out,
-                                                         term_out, lq, st);
-    }
+    with_variant<0>(cfg.phys.model_flags, shape, kind, lq.gains != nullptr,
+                    [&](auto k, auto q, auto lat, auto pm, auto slp, auto) {
+        hipLaunchKernelGGL((cp_rollout_kernel<k.value, q.value, lat.value, pm.value, slp.value>),
+                           layout_grid(0, cfg.num_envs), dim3(WAVE), 0, st, cfg, b, steps, actions, obs_out,
+                           reward_out, done_out, term_out, lq);
+    });
 }
 
 #ifdef CP_POLICY  // the fp32 translation unit only
@@ -1031,23 +1004,6 @@ void launch_policy_act(int kind, const cp_config& cfg, const Bufs& b, const cpc:
         hipLaunchKernelGGL(cp_policy_act_kernel<CP_ACTION_DISCRETE>, grid, block, 0, st, cfg, b, pol);
 }
 #endif  // CP_POLICY
-
-void launch_step(int lat, int kind, const cp_config& cfg, const Bufs& b, const void* actions, float* obs_out,
-                 float* reward_out, uint8_t* done_out, float* term_out, float* readback, int rb_bug, const Lqr& lq,
-                 hipStream_t st) {
-    const bool q = lq.gains != nullptr;
-    if (kind == CP_ACTION_CONTINUOUS) {
-        if (q) launch_step_t<CP_ACTION_CONTINUOUS, true>(lat, cfg, b, actions, obs_out, reward_out, done_out, term_out,
-                                                         readback, rb_bug, lq, st);
-        else launch_step_t<CP_ACTION_CONTINUOUS, false>(lat, cfg, b, actions, obs_out, reward_out, done_out, term_out,
-                                                        readback, rb_bug, lq, st);
-    } else {
-        if (q) launch_step_t<CP_ACTION_DISCRETE, true>(lat, cfg, b, actions, obs_out, reward_out, done_out, term_out,
-                                                       readback, rb_bug, lq, st);
-        else launch_step_t<CP_ACTION_DISCRETE, false>(lat, cfg, b, actions, obs_out, reward_out, done_out, term_out,
-                                                      readback, rb_bug, lq, st);
-    }
-}
 
 #endif  // CP_KERNELS_ONLY
 }  // namespace CP_NS

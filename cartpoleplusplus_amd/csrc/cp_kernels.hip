@@ -18,6 +18,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/cartpole_amd.h"
@@ -152,59 +153,74 @@ struct cp_timing {
 };
 
 struct cp_handle {
-    cp_config cfg;
-    int device;
-    cpc::Bufs b;
-    int f64;           // cfg.precision == CP_PRECISION_F64: real = double (namespace cp64)
-    float* readback;
-    int readback_bug;
-    cpc::Lqr lqr;
-    cpc::Pol pol;      // the MLP policy (cp_set_policy): the caller's fields and the handle's scratch
-    bool pol_on;
+    cp_config cfg{};
+    int device = 0;
+    cpc::Bufs b{};
+    int f64 = 0;       // cfg.precision == CP_PRECISION_F64: real = double (namespace cp64)
+    float* readback = nullptr;
+    int readback_bug = 1;
+    cpc::Lqr lqr{};
+    cpc::Pol pol{};    // the MLP policy (cp_set_policy): the caller's fields and the handle's scratch
+    bool pol_on = false;
     cp_timing timing;
-    cp_raster_config raster;
-    uint16_t* pixels;  // raster obs output (NULL: raster off)
-    bool render_v1;    // CP_RENDER_V1=1 at cp_create: the round-3 small-frame render kernel (A/B diagnostic)
-    int32_t* count2;   // [3] reset-list counters: [0] [1] alternating by call (SAME_STEP: each step kernel
+    cp_raster_config raster{};
+    uint16_t* pixels = nullptr;  // raster obs output (NULL: raster off)
+    bool render_v1 = false;  // CP_RENDER_V1=1 at cp_create: the round-3 small-frame render kernel (A/B diagnostic)
+    int32_t* count2 = nullptr;  // [3] reset-list counters: [0] [1] alternating by call (SAME_STEP: each step kernel
                        // and reset launch zeroes the other one; NEXT_STEP: one per reset list), [2] NEXT_STEP's cp_reset list
-    int par;           // counter the next call appends to
+    int par = 0;       // counter the next call appends to
     // CP_AUTORESET_NEXT_STEP: the two reset lists (by call parity), the side stream each one's reset
     // kernel runs on, the events that fork it after the step kernel and join it back, the reset obs
     // the fixup kernel hands out, and the list whose reset is in flight (-1: none)
-    int32_t* nlist[2];
-    hipStream_t nstream[2];
-    hipEvent_t nfork[2], njoin[2];
-    float* nobs;
-    int npar;
-    int ninflight;
-    int reset_lat;     // CP_SHAPE_* of the autoreset kernel: 1 latency (episodes end at different steps), 2 its WIDE layout
-    int step_lat;      // CP_SHAPE_* of the step kernel: 1 latency (every wave gets a SIMD of its own), 2 WIDE
-    int reset_req;     // cp_set_kernel_shape request (CP_SHAPE_AUTO: choose_reset_shape decides)
-    int step_req;
+    int32_t* nlist[2] = {};
+    hipStream_t nstream[2] = {};
+    hipEvent_t nfork[2] = {}, njoin[2] = {};
+    float* nobs = nullptr;
+    int npar = 0;
+    int ninflight = -1;
+    // the CP_SHAPE_* the step and autoreset kernels run on (never CP_SHAPE_AUTO): resolve_shapes sets them from the
+    // cp_set_kernel_shape requests (CP_SHAPE_AUTO: cps::resolve_shapes decides) and the CP_STEP_LATENCY /
+    // CP_RESET_LATENCY knobs as read at cp_create (cps::knob_value)
+    int step_shape = CP_SHAPE_LATENCY, reset_shape = CP_SHAPE_LATENCY;
+    int step_req = CP_SHAPE_AUTO, reset_req = CP_SHAPE_AUTO;
+    int step_knob = -1, reset_knob = -1;
     // SAME_STEP autoreset without early termination: the number of cp_step calls since every env's
     // step counter was 0 (cp_create, cp_reset of all envs), -1 when unknown (a masked reset,
     // cp_set_state, a call captured into a graph).  Fixed-length episodes then end only on calls n
     // with (n + 1) % max_episode_len == 0, and the other calls launch no reset kernel
     // (may_finish; their list is empty).  CP_RESET_EVERY_CALL=1 turns the skip off (diagnostic).
-    int64_t phase;
-    bool reset_every_call;
-    bool captured;     // some call on this handle was captured into a graph: phase tracking off until cp_destroy
+    int64_t phase = 0;  // cp_create: every env's step counter is 0 (and done is 1: they do not step until reset)
+    bool reset_every_call = false;
+    bool captured = false;  // some call on this handle was captured into a graph: phase tracking off until cp_destroy
     std::string err;
 };
 
-static void choose_reset_shape(cp_handle* h);
-// CP_SHAPE_AUTO picks, for the latency-shaped kernels, the widest layout whose waves still fit the chip once
-// (1,024 SIMDs x 64 lanes): for the step kernel 16 lanes per env up to 4,096 envs (C2), 8 up to 8,192, else
-// the two-lane layout; for the reset kernel also one env per wave (64 lanes) up to 1,024 envs.  The reset lists
-// of desynchronised episodes (bounds / LQR termination) have a length only the device knows: tens to hundreds
-// of envs per step, thousands where many episodes reach max_episode_len together, the whole batch at the first
-// cp_reset; CP_SHAPE_LIST launches one kernel per layout and the list's length picks the one that runs
-// (one env per wave for short lists).  Measured in profiles/rd7d_wide, rd7e_wide, rd7m_reset, rd7z_bench,
-// rd8f_list.
-static int wide_shape_for(int envs) {
-    return envs <= 4096 ? CP_SHAPE_WIDE : (envs <= 8192 ? CP_SHAPE_WIDE8 : CP_SHAPE_LATENCY);
+// the handle's instantiation of a launcher (cp_common.h): cp64:: for fp64 handles, cp:: otherwise
+#define CP_LAUNCH(h, fn, ...) ((h)->f64 ? cp64::fn(__VA_ARGS__) : cp::fn(__VA_ARGS__))
+
+// episodes can end early under the LQR policy's done thresholds
+static bool lqr_done(const cp_handle* h) {
+    return h->lqr.gains && (h->lqr.done_pos > 0.0f || h->lqr.done_angle > 0.0f);
 }
-static int wide_reset_shape_for(int envs) { return envs <= 1024 ? CP_SHAPE_WIDE64 : wide_shape_for(envs); }
+
+// the handle's kernel shapes from everything they depend on (cp_shapes.h): at cp_create, and again whenever
+// cp_set_lqr or cp_set_kernel_shape changes one of the inputs
+static void resolve_shapes(cp_handle* h) {
+    cps::ShapeInputs in;
+    in.num_envs = h->cfg.num_envs;
+    in.f64 = h->f64 != 0;
+    in.model_flags = h->cfg.phys.model_flags;
+    in.autoreset = h->cfg.autoreset;
+    in.done_on_bounds = h->cfg.done_on_bounds != 0;
+    in.lqr_done = lqr_done(h);
+    in.step_knob = h->step_knob;
+    in.reset_knob = h->reset_knob;
+    in.step_req = h->step_req;
+    in.reset_req = h->reset_req;
+    const cps::Shapes s = cps::resolve_shapes(in);
+    h->step_shape = s.step;
+    h->reset_shape = s.reset;
+}
 
 static void timing_free(cp_timing& t) {
     for (hipEvent_t e : t.ev) (void)hipEventDestroy(e);
@@ -360,29 +376,15 @@ int cp_create(const cp_config* cfg, int device, cp_handle** out) {
     if (!h) return fail(nullptr, "cp_create: out of memory");
     h->cfg = *cfg;
     h->device = device;
-    h->readback = nullptr;
-    h->readback_bug = 1;
-    h->lqr = cpc::Lqr{nullptr, 0, nullptr, 0.0f, 0.0f};
     h->f64 = cfg->precision == CP_PRECISION_F64;
-    std::memset(&h->pol, 0, sizeof(h->pol));
-    h->pol_on = false;
-    h->pixels = nullptr;
-    {
-        const char* v1 = std::getenv("CP_RENDER_V1");
-        h->render_v1 = v1 && v1[0] == '1';
-    }
-    h->npar = 0;
-    h->ninflight = -1;
-    h->phase = 0;  // every env's step counter is 0 (and done is 1: they do not step until reset)
-    h->captured = false;
-    {
-        const char* rc = std::getenv("CP_RESET_EVERY_CALL");
-        h->reset_every_call = rc && rc[0] == '1';
-    }
-    h->reset_req = h->step_req = CP_SHAPE_AUTO;
-    choose_reset_shape(h);
+    // the environment knobs, read here once
+    auto on = [](const char* name) { return cps::knob_value(std::getenv(name)) == 1; };
+    h->render_v1 = on("CP_RENDER_V1");
+    h->reset_every_call = on("CP_RESET_EVERY_CALL");
+    h->step_knob = cps::knob_value(std::getenv("CP_STEP_LATENCY"));
+    h->reset_knob = cps::knob_value(std::getenv("CP_RESET_LATENCY"));
+    resolve_shapes(h);
     cp_default_raster_config(&h->raster);
-    std::memset(&h->b, 0, sizeof(h->b));
     const size_t B = (size_t)cfg->num_envs;
     const int R = cfg->action_repeats;
     auto fail_free = [&](hipError_t e, const char* what) {
@@ -392,31 +394,33 @@ int cp_create(const cp_config* cfg, int device, cp_handle** out) {
     };
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return fail_free(e, "hipSetDevice");
-#define CP_ALLOC(ptr, bytes)                                   \
-    e = hipMalloc((void**)&(ptr), (bytes));                    \
-    if (e != hipSuccess) return fail_free(e, "hipMalloc " #ptr);
+    // a device buffer, its size written here only; the ones marked `zero` are cleared once all are allocated
+    std::vector<std::pair<void*, size_t>> zeros;
+#define CP_ALLOC(ptr, bytes, zero)                                   \
+    do {                                                             \
+        e = hipMalloc((void**)&(ptr), (bytes));                      \
+        if (e != hipSuccess) return fail_free(e, "hipMalloc " #ptr); \
+        if (zero) zeros.push_back({(ptr), (bytes)});                 \
+    } while (0)
     const size_t rb = h->f64 ? sizeof(double) : sizeof(float);  // bytes of the handle's real type
-    CP_ALLOC(h->b.state, (size_t)CP_STATE_FIELDS * B * rb);
-    CP_ALLOC(h->b.term_obs, (size_t)R * 14 * B * sizeof(float));
-    CP_ALLOC(h->b.bumps, B * (size_t)(cfg->initial_force_steps > 0 ? cfg->initial_force_steps : 1) * 4 * rb);
-    CP_ALLOC(h->b.ret_acc, B * sizeof(float));
-    CP_ALLOC(h->b.last_ret, B * sizeof(float));
-    CP_ALLOC(h->b.last_len, B * sizeof(int32_t));
-    CP_ALLOC(h->b.overflow, B * sizeof(int32_t));
-    CP_ALLOC(h->b.nonfinite, B * sizeof(int32_t));
-    CP_ALLOC(h->b.list, B * sizeof(int32_t));
-    CP_ALLOC(h->count2, 3 * sizeof(int32_t));
-    CP_ALLOC(h->b.scratch, (size_t)CP_SCR_FIELDS * 2 * B * rb);
-    CP_ALLOC(h->b.stamps, CP_STAMP_SLOTS * sizeof(uint64_t));
-    CP_ALLOC(h->b.stepped, B * sizeof(uint8_t));
-    if (cfg->phys.model_flags & CP_MODEL_PERSISTENT) {  // the persistent manifolds, empty
-        CP_ALLOC(h->b.pman, (size_t)CP_PM_FIELDS * 2 * B * rb);
-        e = hipMemset(h->b.pman, 0, (size_t)CP_PM_FIELDS * 2 * B * rb);
-        if (e != hipSuccess) return fail_free(e, "hipMemset");
-    }
+    CP_ALLOC(h->b.state, (size_t)CP_STATE_FIELDS * B * rb, false);
+    CP_ALLOC(h->b.term_obs, (size_t)R * 14 * B * sizeof(float), true);
+    CP_ALLOC(h->b.bumps, B * (size_t)(cfg->initial_force_steps > 0 ? cfg->initial_force_steps : 1) * 4 * rb, true);
+    CP_ALLOC(h->b.ret_acc, B * sizeof(float), false);
+    CP_ALLOC(h->b.last_ret, B * sizeof(float), false);
+    CP_ALLOC(h->b.last_len, B * sizeof(int32_t), false);
+    CP_ALLOC(h->b.overflow, B * sizeof(int32_t), false);
+    CP_ALLOC(h->b.nonfinite, B * sizeof(int32_t), false);
+    CP_ALLOC(h->b.list, B * sizeof(int32_t), false);
+    CP_ALLOC(h->count2, 3 * sizeof(int32_t), true);
+    CP_ALLOC(h->b.scratch, (size_t)CP_SCR_FIELDS * 2 * B * rb, false);
+    CP_ALLOC(h->b.stamps, CP_STAMP_SLOTS * sizeof(uint64_t), true);
+    CP_ALLOC(h->b.stepped, B * sizeof(uint8_t), true);
+    if (cfg->phys.model_flags & CP_MODEL_PERSISTENT)  // the persistent manifolds, empty
+        CP_ALLOC(h->b.pman, (size_t)CP_PM_FIELDS * 2 * B * rb, true);
     if (cfg->autoreset == CP_AUTORESET_NEXT_STEP) {
         for (int k = 0; k < 2; ++k) {
-            CP_ALLOC(h->nlist[k], B * sizeof(int32_t));
+            CP_ALLOC(h->nlist[k], B * sizeof(int32_t), false);
             // non-blocking: no implicit ordering against a caller's legacy default stream
             e = hipStreamCreateWithFlags(&h->nstream[k], hipStreamNonBlocking);
             if (e != hipSuccess) return fail_free(e, "hipStreamCreateWithFlags");
@@ -425,25 +429,15 @@ int cp_create(const cp_config* cfg, int device, cp_handle** out) {
             e = hipEventCreateWithFlags(&h->njoin[k], hipEventDisableTiming);
             if (e != hipSuccess) return fail_free(e, "hipEventCreateWithFlags");
         }
-        CP_ALLOC(h->nobs, (size_t)R * 14 * B * sizeof(float));
-        e = hipMemset(h->nobs, 0, (size_t)R * 14 * B * sizeof(float));
-        if (e != hipSuccess) return fail_free(e, "hipMemset");
+        CP_ALLOC(h->nobs, (size_t)R * 14 * B * sizeof(float), true);
     }
 #undef CP_ALLOC
-    e = hipMemset(h->count2, 0, 3 * sizeof(int32_t));
-    if (e != hipSuccess) return fail_free(e, "hipMemset");
+    for (const auto& z : zeros) {
+        e = hipMemset(z.first, 0, z.second);
+        if (e != hipSuccess) return fail_free(e, "hipMemset");
+    }
     h->b.count = h->count2;
-    h->b.count_next = nullptr;
-    e = hipMemset(h->b.stepped, 0, B * sizeof(uint8_t));
-    if (e != hipSuccess) return fail_free(e, "hipMemset");
-    e = hipMemset(h->b.stamps, 0, CP_STAMP_SLOTS * sizeof(uint64_t));
-    if (e != hipSuccess) return fail_free(e, "hipMemset");
-    e = hipMemset(h->b.term_obs, 0, (size_t)R * 14 * B * sizeof(float));
-    if (e != hipSuccess) return fail_free(e, "hipMemset");
-    e = hipMemset(h->b.bumps, 0, B * (size_t)(cfg->initial_force_steps > 0 ? cfg->initial_force_steps : 1) * 4 * rb);
-    if (e != hipSuccess) return fail_free(e, "hipMemset");
-    if (h->f64) cp64::launch_init(h->cfg, h->b, 0);
-    else cp::launch_init(h->cfg, h->b, 0);
+    CP_LAUNCH(h, launch_init, h->cfg, h->b, 0);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_free(e, "cp_init_kernel");
     e = hipDeviceSynchronize();
@@ -551,44 +545,10 @@ static void use_counter(cp_handle* h) {
     h->par ^= 1;
 }
 
-// Which autoreset kernel shape (cp_reset_kernel<LAT>): episodes that can end early (bounds
-// termination, LQR done thresholds) end at different steps, so every step resets a short list
-// and its latency is the step's; fixed-length episodes end together in bursts (throughput),
-// except in batches small enough that a burst fits one wave per SIMD.
-// The step kernel has the same two shapes, chosen by batch size alone.  CP_RESET_LATENCY=0/1 and
-// CP_STEP_LATENCY=0/1 override (diagnostics).
-static void choose_reset_shape(cp_handle* h) {
-    const bool lqr_done = h->lqr.gains && (h->lqr.done_pos > 0.0f || h->lqr.done_angle > 0.0f);
-    // up to 32,768 envs every wave gets a SIMD of its own even in a full burst (1,024 SIMDs), so
-    // the latency shape is never the slower one there
-    const bool small = h->cfg.num_envs <= 32768;
-    const char* e = std::getenv("CP_RESET_LATENCY");
-    h->reset_lat = (e && (e[0] == '0' || e[0] == '1')) ? e[0] == '1' : (h->cfg.done_on_bounds || lqr_done || small);
-    const char* es = std::getenv("CP_STEP_LATENCY");
-    h->step_lat = (es && (es[0] == '0' || es[0] == '1')) ? es[0] == '1' : small;
-    // the WIDE layout (16 lanes per env) where its extra waves still leave SIMDs idle
-    const bool wide_ok = !h->f64 && !(h->cfg.phys.model_flags & (CP_MODEL_PERSISTENT | CP_MODEL_SLEEPING));
-    if (wide_ok && h->step_lat) h->step_lat = wide_shape_for(h->cfg.num_envs);
-    // Lists of desynchronised episodes: CP_SHAPE_LIST under either autoreset mode (bounds regime, steps 61-260:
-    // SAME_STEP 10.9 M with one env per wave whatever the list's length, 11.1 M two-lane, 13.2 M by the length;
-    // NEXT_STEP 17.6 / 21.5 / 24.9 M; profiles/rd8f_list).  Fixed-length episodes under NEXT_STEP keep the
-    // two-lane reset beside the next call's step kernel.
-    if (wide_ok && h->reset_lat && (h->cfg.done_on_bounds || lqr_done))
-        h->reset_lat = CP_SHAPE_LIST;
-    else if (wide_ok && h->reset_lat && h->cfg.autoreset != CP_AUTORESET_NEXT_STEP)
-        h->reset_lat = wide_reset_shape_for(h->cfg.num_envs);
-    if (h->reset_req != CP_SHAPE_AUTO) h->reset_lat = h->reset_req;
-    if (h->step_req != CP_SHAPE_AUTO) h->step_lat = h->step_req;
-    if (h->f64) h->reset_lat = h->step_lat = 1;  // fp64: the 512-register shape only
-    if (h->cfg.phys.model_flags & (CP_MODEL_PERSISTENT | CP_MODEL_SLEEPING))
-        h->reset_lat = h->step_lat = 1;  // PM, SLEEPING: latency shape only
-}
-
 static int launch_reset_list(cp_handle* h, const cpc::Bufs& b, float* obs_out, hipStream_t st) {
     hipEvent_t* ev = timing_slot(h, 1);
     if (ev) CP_TRY(h, hipEventRecord(ev[0], st));
-    if (h->f64) cp64::launch_reset(true, h->cfg, b, obs_out, st);
-    else cp::launch_reset(h->reset_lat, h->cfg, b, obs_out, st);
+    CP_LAUNCH(h, launch_reset, h->reset_shape, h->cfg, b, obs_out, st);
     if (check(h, hipGetLastError(), "cp_reset_kernel")) return -1;
     if (ev) CP_TRY(h, hipEventRecord(ev[1], st));
     return 0;
@@ -612,8 +572,7 @@ static bool note_capture(cp_handle* h, hipStream_t st) {
 // (phase + 1) % max_episode_len == 0, and nothing else ends an episode.  The step kernel zeroes the next call's counter itself, so a skipped reset launch
 // leaves the counters as a launched one would.
 static bool may_finish(cp_handle* h, hipStream_t st) {
-    const bool lqr_done = h->lqr.gains && (h->lqr.done_pos > 0.0f || h->lqr.done_angle > 0.0f);
-    if (h->reset_every_call || h->captured || h->phase < 0 || h->cfg.done_on_bounds || lqr_done) return true;
+    if (h->reset_every_call || h->captured || h->phase < 0 || h->cfg.done_on_bounds || lqr_done(h)) return true;
     if (h->cfg.max_episode_len <= 0) return true;  // every step ends the episode (done = steps >= limit)
     return (h->phase + 1) % h->cfg.max_episode_len == 0;
 }
@@ -648,24 +607,16 @@ static int step_next_step(cp_handle* h, const void* actions, int action_kind, fl
     b.keep_done = 1;
     hipEvent_t* ev = timing_slot(h, 0);
     if (ev) CP_TRY(h, hipEventRecord(ev[0], st));
-    if (h->f64)
-        cp64::launch_step(true, action_kind, h->cfg, b, actions, obs_out, reward_out, done_out, terminal_obs_out,
-                          h->readback, h->readback_bug, h->lqr, st);
-    else
-        cp::launch_step(h->step_lat, action_kind, h->cfg, b, actions, obs_out, reward_out, done_out,
-                        terminal_obs_out, h->readback, h->readback_bug, h->lqr, st);
+    CP_LAUNCH(h, launch_step, h->step_shape, action_kind, h->cfg, b, actions, obs_out, reward_out, done_out,
+              terminal_obs_out, h->readback, h->readback_bug, h->lqr, st);
     CP_TRY(h, hipGetLastError());
     if (ev) CP_TRY(h, hipEventRecord(ev[1], st));
     CP_TRY(h, hipEventRecord(h->nfork[q], st));
     if (h->ninflight >= 0) {  // the previous call's list: its reset obs are this call's obs
         const int p = h->ninflight;
         CP_TRY(h, hipStreamWaitEvent(st, h->njoin[p], 0));
-        if (h->f64)
-            cp64::launch_nextstep_fixup(h->cfg, h->b, h->nlist[p], h->count2 + p, p, h->nobs, obs_out, reward_out,
-                                        done_out, st);
-        else
-            cp::launch_nextstep_fixup(h->cfg, h->b, h->nlist[p], h->count2 + p, p, h->nobs, obs_out, reward_out,
-                                      done_out, st);
+        CP_LAUNCH(h, launch_nextstep_fixup, h->cfg, h->b, h->nlist[p], h->count2 + p, p, h->nobs, obs_out, reward_out,
+                  done_out, st);
         CP_TRY(h, hipGetLastError());
         CP_TRY(h, hipMemsetAsync(h->count2 + p, 0, sizeof(int32_t), st));
     }
@@ -688,8 +639,7 @@ int cp_reset(cp_handle* h, const uint8_t* env_mask, float* obs_out, void* stream
         b.count = h->count2 + 2;
         b.count_next = nullptr;
         CP_TRY(h, hipMemsetAsync(b.count, 0, sizeof(int32_t), st));
-        if (h->f64) cp64::launch_nextstep_resolve(h->cfg, b, env_mask, h->nobs, obs_out, st);
-        else cp::launch_nextstep_resolve(h->cfg, b, env_mask, h->nobs, obs_out, st);
+        CP_LAUNCH(h, launch_nextstep_resolve, h->cfg, b, env_mask, h->nobs, obs_out, st);
         CP_TRY(h, hipGetLastError());
         return launch_reset_list(h, b, obs_out, st);
     }
@@ -718,12 +668,8 @@ int cp_step(cp_handle* h, const void* actions, int action_kind, float* obs_out, 
     if (h->pixels) CP_TRY(h, hipMemsetAsync(h->b.rcount, 0, sizeof(int32_t), st));
     hipEvent_t* ev = timing_slot(h, 0);
     if (ev) CP_TRY(h, hipEventRecord(ev[0], st));
-    if (h->f64)
-        cp64::launch_step(true, action_kind, h->cfg, h->b, actions, obs_out, reward_out, done_out, terminal_obs_out,
-                          h->readback, h->readback_bug, h->lqr, st);
-    else
-        cp::launch_step(h->step_lat, action_kind, h->cfg, h->b, actions, obs_out, reward_out, done_out,
-                        terminal_obs_out, h->readback, h->readback_bug, h->lqr, st);
+    CP_LAUNCH(h, launch_step, h->step_shape, action_kind, h->cfg, h->b, actions, obs_out, reward_out, done_out,
+              terminal_obs_out, h->readback, h->readback_bug, h->lqr, st);
     CP_TRY(h, hipGetLastError());
     if (ev) CP_TRY(h, hipEventRecord(ev[1], st));
     // autoreset envs were simulated this step, so they are in the render list; the reset
@@ -752,12 +698,8 @@ int cp_rollout(cp_handle* h, int steps, const void* actions, int action_kind, fl
     CP_TRY(h, hipSetDevice(h->device));
     hipEvent_t* ev = timing_slot(h, 0);
     if (ev) CP_TRY(h, hipEventRecord(ev[0], st));
-    if (h->f64)
-        cp64::launch_rollout(true, action_kind, h->cfg, h->b, steps, actions, obs_out, reward_out, done_out,
-                             terminal_obs_out, h->lqr, st);
-    else
-        cp::launch_rollout(h->step_lat != 0, action_kind, h->cfg, h->b, steps, actions, obs_out, reward_out, done_out,
-                           terminal_obs_out, h->lqr, st);
+    CP_LAUNCH(h, launch_rollout, h->step_shape, action_kind, h->cfg, h->b, steps, actions, obs_out, reward_out, done_out,
+              terminal_obs_out, h->lqr, st);
     CP_TRY(h, hipGetLastError());
     if (ev) CP_TRY(h, hipEventRecord(ev[1], st));
     note_capture(h, st);
@@ -859,7 +801,7 @@ int cp_set_lqr(cp_handle* h, const float* gains, int per_env, float* state8_out,
     h->lqr.state8 = state8_out;
     h->lqr.done_pos = done_pos;
     h->lqr.done_angle = done_angle;
-    choose_reset_shape(h);
+    resolve_shapes(h);
     return 0;
 }
 
@@ -902,33 +844,18 @@ int64_t cp_state_bytes(const cp_handle* h) {
 
 int cp_set_kernel_shape(cp_handle* h, int step_shape, int reset_shape) {
     if (!h) return fail(h, "cp_set_kernel_shape: null handle");
-    auto ok = [](int v) {
-        return v == CP_SHAPE_AUTO || v == CP_SHAPE_THROUGHPUT || v == CP_SHAPE_LATENCY || v == CP_SHAPE_WIDE ||
-               v == CP_SHAPE_WIDE8 || v == CP_SHAPE_WIDE64 || v == CP_SHAPE_LIST;
-    };
-    if (!ok(step_shape) || !ok(reset_shape))
-        return fail(h, "cp_set_kernel_shape: shapes must be CP_SHAPE_AUTO, CP_SHAPE_THROUGHPUT, CP_SHAPE_LATENCY, "
-                       "CP_SHAPE_WIDE, CP_SHAPE_WIDE8, CP_SHAPE_WIDE64 or CP_SHAPE_LIST");
-    auto fixed = [](int v) {
-        return v == CP_SHAPE_THROUGHPUT || v == CP_SHAPE_WIDE || v == CP_SHAPE_WIDE8 || v == CP_SHAPE_WIDE64 ||
-               v == CP_SHAPE_LIST;
-    };
-    if (step_shape == CP_SHAPE_WIDE64 || step_shape == CP_SHAPE_LIST)
-        return fail(h, "cp_set_kernel_shape: CP_SHAPE_WIDE64 and CP_SHAPE_LIST are reset-kernel layouts");
-    if ((h->f64 || (h->cfg.phys.model_flags & (CP_MODEL_PERSISTENT | CP_MODEL_SLEEPING))) &&
-        (fixed(step_shape) || fixed(reset_shape)))
-        return fail(h, "cp_set_kernel_shape: fp64, persistent-manifold and sleeping-model handles have the latency "
-                       "shape only");
+    if (const char* why = cps::check_requests(h->f64 != 0, h->cfg.phys.model_flags, step_shape, reset_shape))
+        return fail(h, std::string("cp_set_kernel_shape: ") + why);
     h->step_req = step_shape;
     h->reset_req = reset_shape;
-    choose_reset_shape(h);
+    resolve_shapes(h);
     return 0;
 }
 
 int cp_get_kernel_shape(const cp_handle* h, int* step_shape, int* reset_shape) {
     if (!h) return fail(nullptr, "cp_get_kernel_shape: null handle");
-    if (step_shape) *step_shape = h->step_lat;
-    if (reset_shape) *reset_shape = h->reset_lat;
+    if (step_shape) *step_shape = h->step_shape;
+    if (reset_shape) *reset_shape = h->reset_shape;
     return 0;
 }
 
