@@ -330,6 +330,36 @@ __global__ void __launch_bounds__(256) cp_init_kernel(cp_config cfg, Bufs b) {
     b.nonfinite[i] = 0;
 }
 
+// The start of an env's reset, on the lane's own island (the reset kernel's prologue, and cp_rollout's in-launch
+// autoreset): spawn poses, and nothing of the old episode's contacts left in the caches.
+template <bool PM, bool SLP>
+CP_DEV void begin_reset(Own& O, const cp_config& cfg, const Mem& G, bool second) {
+    O.f = reset_force(cfg, O.f);  // pending forces survive the reset (pybullet keeps them)
+    spawn_own(O, cfg, second);
+    if constexpr (SLP) sleep_wake_all(O);  // the teleported bodies are awake
+#pragma unroll
+    for (int j = 0; j < CP_ISLAND_PAIRS; ++j) {  // the lane's island's warm-start cache
+        G.sw(CP_SF_WS_ID(0, j), bits_to<real>(0xFFFFFFFFu));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) G.sl(CP_SF_WS_LAM(0, j, k), real(0.0));
+        // resetBasePositionAndOrientation: no cached contact survives the teleport
+        if constexpr (PM) G.sp(pmf(j, 0), bits_to<real>(0u));
+    }
+    O.wsm = 0u;
+}
+
+// Wave-ballot list append: the lanes with `want` append `value` to the list, one atomic on its counter per
+// wave (lane 0) and a prefix popcount for each lane's slot.  Called by every lane of the wave.
+CP_DEV void wave_append(bool want, int32_t* counter, int32_t* list, int value) {
+    const uint64_t bal = __ballot(want);
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int n = __popcll(bal);
+    int base = 0;
+    if (lane == 0 && n) base = atomicAdd(counter, n);
+    base = __shfl(base, 0);
+    if (want) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = value;
+}
+
 // LAT = false: the throughput shape of the step kernel (2 waves per SIMD), for reset bursts
 // (fixed-length episodes end together).  LAT = true: one wave per SIMD with 512 registers and
 // fast-form rows, for the short lists of desynchronised episodes (bounds termination), where
@@ -371,20 +401,9 @@ cp_reset_kernel(cp_config cfg, Bufs b, float* obs_out) {
     CP_RT(r0);
     const bool second = isl != 0;
     Own O;
-    load_own(O, G, isl);  // pending forces survive the reset (pybullet keeps them)
-    O.f = reset_force(cfg, O.f);
-    if constexpr (PM)  // resetBasePositionAndOrientation: no cached contact survives the teleport
-        for (int j = 0; j < CP_ISLAND_PAIRS; ++j) G.sp(pmf(j, 0), bits_to<real>(0u));
+    load_own(O, G, isl);
     const int episode = ldi(G.st, CP_SF_EPISODE, G.off);
-    spawn_own(O, cfg, second);
-    if constexpr (SLP) sleep_wake_all(O);  // the teleported bodies are awake
-#pragma unroll
-    for (int j = 0; j < CP_ISLAND_PAIRS; ++j) {  // the lane's island's warm-start cache
-        G.sw(CP_SF_WS_ID(0, j), bits_to<real>(0xFFFFFFFFu));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) G.sl(CP_SF_WS_LAM(0, j, k), real(0.0));
-    }
-    O.wsm = 0u;
+    begin_reset<PM, SLP>(O, cfg, G, second);
     int ov = 0;
     const int nsub = cfg.settle_steps + cfg.initial_force_steps;
     for (int s = 0; s < nsub; ++s) {
@@ -424,6 +443,25 @@ cp_reset_kernel(cp_config cfg, Bufs b, float* obs_out) {
     if (!b.keep_done) sti(Ge.st, CP_SF_DONE, Ge.off, 0);  // NEXT_STEP in flight: the fixup kernel clears it
     sti(Ge.st, CP_SF_EPISODE, Ge.off, episode + 1);
     b.ret_acc[il] = 0.0f;
+}
+
+// One env-step's action forces, action_force * action (bullet_cartpole.py:201-207): continuous
+// float4 (a00 a01 a10 a11) or discrete int8 x 2 through kDiscrete (out-of-range index = 0).
+template <int KIND>
+CP_DEV void action_forces(const void* actions, size_t row, real F, real f[4]) {
+    real a00, a01, a10, a11;
+    if constexpr (KIND == CP_ACTION_CONTINUOUS) {
+        const float4 a = reinterpret_cast<const float4*>(actions)[row];
+        a00 = a.x; a01 = a.y; a10 = a.z; a11 = a.w;
+    } else {
+        const char2 a = reinterpret_cast<const char2*>(actions)[row];
+        int k0 = a.x, k1 = a.y;
+        k0 = (k0 < 0 || k0 >= CP_NUM_DISCRETE) ? 0 : k0;
+        k1 = (k1 < 0 || k1 >= CP_NUM_DISCRETE) ? 0 : k1;
+        a00 = kDiscrete[k0][0]; a01 = kDiscrete[k0][1];
+        a10 = kDiscrete[k1][0]; a11 = kDiscrete[k1][1];
+    }
+    f[0] = a00 * F; f[1] = a01 * F; f[2] = a10 * F; f[3] = a11 * F;
 }
 
 // LAT: the latency shape of cp_reset_kernel<true> (1 wave per SIMD, 512 registers, fast-form
@@ -488,22 +526,11 @@ cp_step_kernel(cp_config cfg, Bufs b, const void* actions, float* obs_out, float
                 done_out[i] = 1;
             }
         } else {
-            real a00, a01, a10, a11;
-            if constexpr (KIND == CP_ACTION_CONTINUOUS) {
-                const float4 a = reinterpret_cast<const float4*>(actions)[i];
-                a00 = a.x; a01 = a.y; a10 = a.z; a11 = a.w;
-            } else {
-                const char2 a = reinterpret_cast<const char2*>(actions)[i];
-                int k0 = a.x, k1 = a.y;
-                k0 = (k0 < 0 || k0 >= CP_NUM_DISCRETE) ? 0 : k0;
-                k1 = (k1 < 0 || k1 >= CP_NUM_DISCRETE) ? 0 : k1;
-                a00 = kDiscrete[k0][0]; a01 = kDiscrete[k0][1];
-                a10 = kDiscrete[k1][0]; a11 = kDiscrete[k1][1];
-            }
-            const real F = cfg.action_force;
+            real f[4];
+            action_forces<KIND>(actions, (size_t)i, real(cfg.action_force), f);
             const bool second = isl != 0;
             // the lane's own cart's action force (action[0] -> cart, action[1] -> cart2, :201-207)
-            const real fa = (second ? a10 : a00) * F, fb = (second ? a11 : a01) * F;
+            const real fa = second ? f[2] : f[0], fb = second ? f[3] : f[1];
             Own O;
             load_own(O, G, isl);
             if constexpr (SLP) load_sleep(O, G, isl);
@@ -590,43 +617,10 @@ cp_step_kernel(cp_config cfg, Bufs b, const void* actions, float* obs_out, float
     flush_stamps(ST, b.stamps, k1 - k0, r0, r1, b.stamps);
 #endif
     if (cfg.autoreset) {
-        // wave ballot compaction of the finishing envs into the reset list
-        const uint64_t bal = __ballot(want_reset);
-        const int lane = threadIdx.x;  // want_reset is set on lead lanes only
-        const int n = __popcll(bal);
-        int base = 0;
-        if (lane == 0 && n) base = atomicAdd(b.count, n);
-        base = __shfl(base, 0);
-        if (want_reset) b.list[base + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+        // the finishing envs into the reset list (want_reset is set on lead lanes only)
+        wave_append(want_reset, b.count, b.list, i);
     }
-    if (b.rposes) {
-        const uint64_t bal = __ballot(render_me);
-        const int lane = threadIdx.x & (WAVE - 1);
-        const int n = __popcll(bal);
-        int base = 0;
-        if (lane == 0 && n) base = atomicAdd(b.rcount, n);
-        base = __shfl(base, 0);
-        if (render_me) b.rlist[base + __popcll(bal & ((1ull << lane) - 1ull))] = i;
-    }
-}
-
-// One env-step's action forces, action_force * action (bullet_cartpole.py:201-207): continuous
-// float4 (a00 a01 a10 a11) or discrete int8 x 2 through kDiscrete (out-of-range index = 0).
-template <int KIND>
-CP_DEV void action_forces(const void* actions, size_t row, real F, real f[4]) {
-    real a00, a01, a10, a11;
-    if constexpr (KIND == CP_ACTION_CONTINUOUS) {
-        const float4 a = reinterpret_cast<const float4*>(actions)[row];
-        a00 = a.x; a01 = a.y; a10 = a.z; a11 = a.w;
-    } else {
-        const char2 a = reinterpret_cast<const char2*>(actions)[row];
-        int k0 = a.x, k1 = a.y;
-        k0 = (k0 < 0 || k0 >= CP_NUM_DISCRETE) ? 0 : k0;
-        k1 = (k1 < 0 || k1 >= CP_NUM_DISCRETE) ? 0 : k1;
-        a00 = kDiscrete[k0][0]; a01 = kDiscrete[k0][1];
-        a10 = kDiscrete[k1][0]; a11 = kDiscrete[k1][1];
-    }
-    f[0] = a00 * F; f[1] = a01 * F; f[2] = a10 * F; f[3] = a11 * F;
+    if (b.rposes) wave_append(render_me, b.rcount, b.rlist, i);
 }
 
 // cp_rollout: K consecutive env-steps of every env in one launch, bit for bit the outputs and
@@ -770,18 +764,8 @@ cp_rollout_kernel(cp_config cfg, Bufs b, int K, const void* actions, float* obs_
                         for (int q = 0; q < R * 14; ++q) term_out[(size_t)k * obs_step + e * R * 14 + q] = obs[q];
                 }
                 flags |= RF_DONE;
-                if (cfg.autoreset) {  // the reset kernel's prologue: pending forces survive
-                    O.f = reset_force(cfg, O.f);
-                    spawn_own(O, cfg, second);
-                    if constexpr (SLP) sleep_wake_all(O);
-#pragma unroll
-                    for (int j = 0; j < CP_ISLAND_PAIRS; ++j) {
-                        G.sw(CP_SF_WS_ID(0, j), bits_to<real>(0xFFFFFFFFu));
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) G.sl(CP_SF_WS_LAM(0, j, q), real(0.0));
-                        if constexpr (PM) G.sp(pmf(j, 0), bits_to<real>(0u));
-                    }
-                    O.wsm = 0u;
+                if (cfg.autoreset) {  // the reset kernel's prologue
+                    begin_reset<PM, SLP>(O, cfg, G, second);
                     stc(RC_SUB, 0);
                     stc(RC_STEPS, steps);
                     stc(RC_FLAGS, (int)(flags | RF_RESETTING));
@@ -870,13 +854,7 @@ __global__ void __launch_bounds__(256) cp_nextstep_resolve_kernel(cp_config cfg,
             want = true;
         }
     }
-    const uint64_t bal = __ballot(want);
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int n = __popcll(bal);
-    int base = 0;
-    if (lane == 0 && n) base = atomicAdd(b.count, n);
-    base = __shfl(base, 0);
-    if (want) b.list[base + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+    wave_append(want, b.count, b.list, i);
 }
 
 // ---------------------------------------------------------------- host launchers

@@ -44,13 +44,7 @@ __global__ void __launch_bounds__(256) cp_mask_to_list_kernel(int B, const uint8
                                                                int32_t* count) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     bool want = i < B && (mask == nullptr || mask[i] != 0);
-    uint64_t bal = __ballot(want);
-    int lane = threadIdx.x & (WAVE - 1);
-    int n = __popcll(bal);
-    int base = 0;
-    if (lane == 0 && n) base = atomicAdd(count, n);
-    base = __shfl(base, 0);
-    if (want) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+    wave_append(want, count, list, i);
 }
 
 // ---------------------------------------------------------------------------

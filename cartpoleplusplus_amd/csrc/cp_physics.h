@@ -688,6 +688,23 @@ CP_DEV bool isl_row_ez(Isl& I, V3 rb, real inv_eff, real target, real& lam, real
 }
 CP_DEV bool is_plus_z(V3 n) { return n.x == real(0.0) && n.y == real(0.0) && n.z == real(1.0); }
 
+// One normal row of the lane's pool column (the LDS-row loops): slot s through isl_row along t, or through
+// isl_row_ez (ground pair, +z normal), and its impulse back into the slot.
+template <int A, int B>
+CP_DEV void pool_row(Isl& I, real* pool, int s, V3 t, real tol, bool& bad) {
+    const V3 rb = mk(pool_n(pool, F_RBX, s), pool_n(pool, F_RBY, s), pool_n(pool, F_RBZ, s));
+    real lam = pool_n(pool, F_LAM, s);
+    bad |= isl_row<A, B, false>(I, rb, t, pool_n(pool, F_IE, s), pool_n(pool, F_TG, s), lam, real(0.0), tol);
+    pool_n(pool, F_LAM, s) = lam;
+}
+template <int B>
+CP_DEV void pool_row_ez(Isl& I, real* pool, int s, real tol, bool& bad) {
+    const V3 rb = mk(pool_n(pool, F_RBX, s), pool_n(pool, F_RBY, s), pool_n(pool, F_RBZ, s));
+    real lam = pool_n(pool, F_LAM, s);
+    bad |= isl_row_ez<B, 0, false>(I, rb, pool_n(pool, F_IE, s), pool_n(pool, F_TG, s), lam, real(0.0), tol);
+    pool_n(pool, F_LAM, s) = lam;
+}
+
 // local pair j (0..2) of the island: (ground, cart), (ground, pole), (cart, pole)
 template <int J> constexpr int loc_a() { return J == 2 ? 1 : 0; }
 template <int J> constexpr int loc_b() { return J == 0 ? 1 : 2; }
@@ -759,13 +776,7 @@ CP_DEV void isl_normal_rows_ez(Isl& I, const Step& T, real* pool, real tol, bool
     static_assert(loc_a<J>() == 0, "ground pairs only");
     const uint32_t pk = T.pk[J];
     const int cnt = pk_cnt(pk), base = pk_base(pk);
-    CP_EZ_LOOP(k, cnt) {
-        const int s = base + k;
-        V3 rb = mk(pool_n(pool, F_RBX, s), pool_n(pool, F_RBY, s), pool_n(pool, F_RBZ, s));
-        real lam = pool_n(pool, F_LAM, s);
-        bad |= isl_row_ez<loc_b<J>(), 0, false>(I, rb, pool_n(pool, F_IE, s), pool_n(pool, F_TG, s), lam, real(0.0), tol);
-        pool_n(pool, F_LAM, s) = lam;
-    }
+    CP_EZ_LOOP(k, cnt) pool_row_ez<loc_b<J>()>(I, pool, base + k, tol, bad);
 }
 template <int J>
 CP_DEV void isl_friction_rows_ez(Isl& I, const Step& T, real mu, real* pool, real tol, bool& bad) {
@@ -1183,104 +1194,68 @@ struct Ctx {
     uint32_t slp;    // CP_MODEL_SLEEPING: the bodies that sleep this step (bit d = dynamic body d); else 0
 };
 
-// One PGS sweep range [it0, it1) over the lane's island (+ the cross rows of a merged
-// env).  S supplies positions for the cross rows and is scratch for their whole-env
-// view.  Both lanes of an env stop together, after the first sweep in which no row of
-// the env (island 0, island 1, cross) has a squared residual above the threshold:
-// Bullet solves the two islands as one group (oracle: substep, step 4).
-CP_DEV bool c44_ok(const Ctx& c);
+// The cross rows of a merged env (global pairs 5-8), one KIND of them: the whole-env view from both lanes'
+// islands, the four pairs in the oracle's order, and the solved velocities back into the lane's island.  Both
+// lanes of the env run it on the same values.  X_WARM: the warm-start impulses (tol and badc unused).
+enum : int { X_NORMAL, X_FRICTION, X_WARM };
+template <int KIND, bool PM, int PAIR>
+CP_DEV void cross_pair(Sim& S, const Step& T, bool second, const cp_physics& P, real* pool0, real tol, bool& badc) {
+    if constexpr (KIND == X_NORMAL) pair_normal_rows<PAIR, PM>(S, T, second, P, pool0, tol, badc);
+    else if constexpr (KIND == X_FRICTION) pair_friction_rows<PAIR, PM>(S, T, second, P, pool0, tol, badc);
+    else pair_warmstart<PAIR, PM>(S, T, second, P, pool0);
+}
+template <int KIND, bool PM = false>
+CP_DEV void cross_rows(Sim& S, Ctx& c, bool second, const cp_physics& P, real* pool0, real tol, bool& badc) {
+    cross_view(S, c.T, c.I, second);
+    cross_pair<KIND, PM, 5>(S, c.T, second, P, pool0, tol, badc);
+    cross_pair<KIND, PM, 6>(S, c.T, second, P, pool0, tol, badc);
+    cross_pair<KIND, PM, 7>(S, c.T, second, P, pool0, tol, badc);
+    cross_pair<KIND, PM, 8>(S, c.T, second, P, pool0, tol, badc);
+    cross_back(c.I, S, second);
+}
+
+// ---- the row structures a whole wave can be in (wave-uniform choices of solve_range, solve_lean and the
+// reset kernels' general loops)
+// No friction rows on local pairs 0 / 2 (the default friction table: a cart's friction is 0): the fast form.
+CP_DEV bool fast_ok(const Ctx& c) { return pk_fcnt(c.T.pk[0]) == 0 && pk_fcnt(c.T.pk[2]) == 0; }
+
+// The settle structure: the island's cart on the ground (4 rows of local pair 0, normal
+// exactly +z) and its pole standing on the cart (4 rows of local pair 2), no other rows, no
+// cross contact.  Every island of a reset's 100 settle substeps, and ~85 % of the islands
+// that run to the sweep cap in the step (DESIGN.md §5).
+CP_DEV bool c44_ok(const Ctx& c) {
+    // no friction rows on pairs 0 and 2: the reference scene's cart has mu = 0 (cart.urdf), so its pairs have
+    // none, but a configured cart friction gives them some, and the settle loops do not run them
+    return pk_cnt(c.T.pk[0]) == 4 && pk_cnt(c.T.pk[2]) == 4 && pk_cnt(c.T.pk[1]) == 0 && !c.merged &&
+           is_plus_z(c.T.n[0]) && pk_fcnt(c.T.pk[0]) == 0 && pk_fcnt(c.T.pk[2]) == 0;
+}
+
+// The bump phase's structures: the cart on the ground (4 rows of local pair 0, normal exactly +z) and
+// 0-4 rows of its pole on the cart (a tilting or bouncing pole), no pole-ground rows, no cross contact.
+// ~94 % of the island-substeps of a reset's 30 bump substeps that are not the settle structure
+// (oracle ORC_STATS run of 256 resets).
+CP_DEV bool c4k_ok(const Ctx& c) {
+    return pk_cnt(c.T.pk[0]) == 4 && pk_cnt(c.T.pk[1]) == 0 && !c.merged && is_plus_z(c.T.n[0]) &&
+           pk_fcnt(c.T.pk[0]) == 0 && pk_fcnt(c.T.pk[2]) == 0;
+}
+
+// The step kernels' dominant island (tools/row_classes.py: 94 % of the C3 steady state's island
+// solves, and nearly all of the sweep-cap stragglers): the pole standing on the ground on its 1 cm
+// base (local pair 1: 4 normal rows and 4 friction points, normal exactly +z), its cart either off
+// the ground or standing on it (local pair 0: 0 or 4 rows, +z), nothing on the cart-pole pair, no
+// friction rows on pairs 0 / 2, no cross contact.
+CP_DEV bool p1_ok(const Ctx& c) {
+    const int c0 = pk_cnt(c.T.pk[0]);
+    return pk_cnt(c.T.pk[1]) == 4 && pk_fcnt(c.T.pk[1]) == 4 && is_plus_z(c.T.n[1]) && pk_cnt(c.T.pk[2]) == 0 &&
+           pk_fcnt(c.T.pk[0]) == 0 && pk_fcnt(c.T.pk[2]) == 0 && !c.merged &&
+           (c0 == 0 || (c0 == 4 && is_plus_z(c.T.n[0])));
+}
+
 // how often (in sweeps) the reset kernels' sweep loops re-test whether every active lane of the wave
 // has the settle structure (the lanes without it usually converge first)
 constexpr int kC44Check = 8;
-CP_DEV bool c4k_ok(const Ctx& c);
-CP_DEV void sweeps_c44_slow(Ctx& c, real* pool, real tol, int it0, int it1, Stamps& ST);
-CP_DEV void sweeps_c4k_slow(Ctx& c, real* pool, real tol, int it0, int it1, Stamps& ST);
-CP_DEV bool p1_ok(const Ctx& c);
 // sweeps into a solve after which the throughput step kernels' wave raises its issue priority
 constexpr int kPrioAfter = 16;
-// HX = false: no env of the wave is merged (checked by the caller), so the cross-row blocks and the merge of
-// their results into the island view are compiled out of the sweep
-template <bool C44 = false, bool PM = false, bool HX = true>
-CP_DEV void sweeps(Ctx& c, Sim& S, const cp_physics& P, real* pool, real* pool0, bool second, int it0, int it1,
-                   Stamps& ST) {
-    const real tol = sqrt_(real(P.residual_threshold));  // oracle: SQRT((real)threshold)
-    // the ground-pole pair's tangent basis (with the URDF frictions the only island pair with
-    // friction rows: the carts' friction is 0), once per substep instead of once per sweep:
-    // step kernel 0.772 -> 0.753 ms
-    V3 h1 = mk(real(0.0), real(0.0), real(0.0)), h2 = h1;
-    if constexpr (!PM) plane_space(c.T.n[1], h1, h2);
-    // ground pairs whose rows all have a +z normal in this wave run isl_row_ez (wave-uniform):
-    // the ground-pole pair in every measured wave, the ground-cart pair in ~3 of 4 (PM: every row
-    // has its own normal, the generic rows)
-    const bool ez0 = !PM && __ballot(pk_cnt(c.T.pk[0]) > 0 && !is_plus_z(c.T.n[0])) == 0ull;
-    const bool ez1 = !PM && __ballot(pk_cnt(c.T.pk[1]) > 0 && !is_plus_z(c.T.n[1])) == 0ull;
-#ifdef CP_STAMPS
-    ST.flags |= (ez0 ? 0u : 2u) | (ez1 ? 0u : 4u);
-#endif
-    for (int it = it0; it < it1; ++it) {
-        if (__ballot(c.active) == 0ull) break;
-        // a wave deep into a long solve (a capped env: the launch's tail) takes its SIMD's issue
-        // priority from its co-resident partner: C3 +1.2 % (threshold 8, 16 or 30 alike)
-        if constexpr (!C44) {
-            if (it == it0 + kPrioAfter) {
-                __builtin_amdgcn_s_setprio(1);
-            }
-        }
-        if constexpr (C44 && !PM) {  // every still-active lane in the settle structure (the reset kernels)
-            if ((it - it0) % kC44Check == 0 && __ballot(c.active && !c44_ok(c)) == 0ull) {
-                sweeps_c44_slow(c, pool, tol, it, it1, ST);
-                return;
-            }
-            if (it == it0 && __ballot(c.active && !c4k_ok(c)) == 0ull) {  // the bump phase's structures
-                sweeps_c4k_slow(c, pool, tol, it, it1, ST);
-                return;
-            }
-        }
-#ifdef CP_STAMPS
-        ST.sweeps += 1;
-#endif
-        bool bad = false, badc = false;
-        if (c.active) {
-            if (ez0) isl_normal_rows_ez<0>(c.I, c.T, pool, tol, bad);
-            else isl_normal_rows<0, PM>(c.I, c.T, pool, tol, bad);
-            if (ez1) isl_normal_rows_ez<1>(c.I, c.T, pool, tol, bad);
-            else isl_normal_rows<1, PM>(c.I, c.T, pool, tol, bad);
-            isl_normal_rows<2, PM>(c.I, c.T, pool, tol, bad);
-        }
-        const bool cross = HX && c.active && c.merged;  // same on both lanes of an env
-        if (HX && __ballot(cross) != 0ull && cross) {
-            cross_view(S, c.T, c.I, second);
-            pair_normal_rows<5, PM>(S, c.T, second, P, pool0, tol, badc);
-            pair_normal_rows<6, PM>(S, c.T, second, P, pool0, tol, badc);
-            pair_normal_rows<7, PM>(S, c.T, second, P, pool0, tol, badc);
-            pair_normal_rows<8, PM>(S, c.T, second, P, pool0, tol, badc);
-            cross_back(c.I, S, second);
-        }
-        if (c.active) {
-            if (ez0) isl_friction_rows_ez<0>(c.I, c.T, c.mu0, pool, tol, bad);
-            else isl_friction_rows<0, false, PM>(c.I, c.T, c.mu0, pool, tol, bad);
-            if (ez1) isl_friction_rows_ez<1>(c.I, c.T, c.mu1, pool, tol, bad);
-            else if (PM) isl_friction_rows<1, false, PM>(c.I, c.T, c.mu1, pool, tol, bad);
-            else isl_friction_rows<1, true>(c.I, c.T, c.mu1, pool, tol, bad, h1, h2);
-            isl_friction_rows<2, false, PM>(c.I, c.T, c.mu2, pool, tol, bad);
-        }
-        // the friction half only where a cross pair has friction rows: cross_view + cross_back alone
-        // change no value (the whole-env view and back), and a wave with a merged env pays them per sweep
-        const bool crossf = cross && c.xfric;
-        if (HX && __ballot(crossf) != 0ull && crossf) {
-            cross_view(S, c.T, c.I, second);
-            pair_friction_rows<5, PM>(S, c.T, second, P, pool0, tol, badc);
-            pair_friction_rows<6, PM>(S, c.T, second, P, pool0, tol, badc);
-            pair_friction_rows<7, PM>(S, c.T, second, P, pool0, tol, badc);
-            pair_friction_rows<8, PM>(S, c.T, second, P, pool0, tol, badc);
-            cross_back(c.I, S, second);
-        }
-        // every lane that entered the loop is here (pairs together): the env's joint decision
-        const uint32_t pbad = partner_u(bad ? 1u : 0u);
-        if (c.active && !bad && !badc && pbad == 0u) c.active = false;
-    }
-    if constexpr (!C44) __builtin_amdgcn_s_setprio(0);
-}
 
 // ---- fast-form island rows.  Bullet's sequential-impulse solver
 // precomputes, per solver row, the lever-arm cross product r x t and the angular
@@ -1317,8 +1292,6 @@ struct FastIslT {
     V3 t1, t2;              // their tangents (plane_space of pair 1's normal)
 };
 using FastIsl = FastIslT<true>;
-
-CP_DEV bool fast_ok(const Ctx& c) { return pk_fcnt(c.T.pk[0]) == 0 && pk_fcnt(c.T.pk[2]) == 0; }
 
 template <int J>
 CP_DEV void fast_ground_rows(GRow* R, const Ctx& c, real* pool) {
@@ -1363,7 +1336,7 @@ CP_DEV void fast_cart_pole_rows(CRow* C, const Ctx& c, real* pool) {
 
 // The rows of the settle-loop structures alone (c4k_ok: local pair 0 in +z form, 0-4 cart-pole rows,
 // nothing else): the latency reset kernels' common case.  Built apart from FastIsl so that only these
-// ~100 values are live through sweeps_c44 / sweeps_c4k (with the whole FastIsl live, the register
+// ~100 values are live through sweeps_c4 (with the whole FastIsl live, the register
 // allocator parked a third of them in AGPRs: 50 v_accvgpr_read per settle sweep of 279 instructions)
 struct FastC4 {
     GRow g0[4];
@@ -1473,195 +1446,193 @@ CP_DEV bool fast_crow(Isl& I, V3 t, const CRow& R, real& lam, real tol) {
     return abs_(dl) > tol * R.ie;  // Bullet residual test (oracle: solve_row)
 }
 
-// The settle structure: the island's cart on the ground (4 rows of local pair 0, normal
-// exactly +z) and its pole standing on the cart (4 rows of local pair 2), no other rows, no
-// cross contact.  Every island of a reset's 100 settle substeps, and ~85 % of the islands
-// that run to the sweep cap in the step (DESIGN.md §5).
-CP_DEV bool c44_ok(const Ctx& c) {
-    // no friction rows on pairs 0 and 2: the reference scene's cart has mu = 0 (cart.urdf), so its pairs have
-    // none, but a configured cart friction gives them some, and the settle loops do not run them
-    return pk_cnt(c.T.pk[0]) == 4 && pk_cnt(c.T.pk[2]) == 4 && pk_cnt(c.T.pk[1]) == 0 && !c.merged &&
-           is_plus_z(c.T.n[0]) && pk_fcnt(c.T.pk[0]) == 0 && pk_fcnt(c.T.pk[2]) == 0;
+// ---- row groups in fast form: one local pair's rows of one sweep, for the structure loops (their pairs hold
+// all 4 rows, so no per-row guard).  sweeps_fast() keeps its guarded rows written out: built from these groups
+// with a run-time count its kernels' register allocation changed (WIDE16 reset 470 -> 471 VGPRs, latency step
+// 441 -> 442).
+// the 4 normal rows of a ground pair in +z form on body b (local pair 0: the cart, 1: the pole)
+CP_DEV void ground_rows_ez(GRow* R, Dyn& b, real imb, real tol, bool& bad) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        bad |= fast_grow_ez<0, false>(b, imb, R[k].rbt, R[k].ib, R[k].ie, R[k].tg, R[k].lam, real(0.0), tol);
 }
 
-// sweeps_fast when every active lane of the wave has the settle structure: the same rows in
-// the same order (4 ground rows in +z form, then 4 cart-pole rows; no friction, no cross
-// rows), straight-line, without the per-row lane guards of the general loop.
-template <class FI>
-CP_DEV void sweeps_c44(Ctx& c, FI& F, real tol, int it0, int it1, Stamps& ST) {
-    const V3 n2 = c.T.n[2];
+// the cart-pole pair's normal rows: all 4 (FULL) or guarded by the lane's own count
+template <bool FULL>
+CP_DEV void cart_pole_rows(CRow* C, Isl& I, V3 n2, real tol, bool& bad, int cnt) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (FULL || k < cnt) bad |= fast_crow(I, n2, C[k], C[k].lam, tol);
+}
+
+// the island rows' impulses back into the pool (substep_finish refreshes the
+// warm-start cache from it)
+template <bool HC2>
+CP_DEV void fast_store(const FastIslT<HC2>& F, const Ctx& c, real* pool) {
+    const int cnt0 = pk_cnt(c.T.pk[0]), cnt1 = pk_cnt(c.T.pk[1]), cnt2 = pk_cnt(c.T.pk[2]);
+    const int b0 = pk_base(c.T.pk[0]), b1 = pk_base(c.T.pk[1]), b2 = pk_base(c.T.pk[2]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k < cnt0) pool_n(pool, F_LAM, b0 + k) = F.g0[k].lam;
+        if (k < cnt1) pool_n(pool, F_LAM, b1 + k) = F.g1[k].lam;
+        if constexpr (HC2)
+            if (k < cnt2) pool_n(pool, F_LAM, b2 + k) = F.c2[k].lam;
+    }
+}
+
+// ---- the sweep skeleton: PGS sweeps [it0, it1) of the wave's lanes and their stopping rule.
+// Both lanes of an env stop together, after the first sweep in which no row of the env (island 0,
+// island 1, cross) has a residual above the threshold: Bullet solves the two islands as one group
+// (oracle: substep, step 4).  So a lane leaves only when its own island rows (bad) and its partner's (pbad)
+// all passed.  Every lane that entered the loop reaches the partner exchange (pairs together); the wave
+// leaves when no lane is active.  rows() runs one sweep's rows on the active lanes and returns bad.
+// The structure loops' CP_STAMPS sweep counter lives here: a sweep counts once, whichever loop runs it.
+// (The general loops, sweeps() and sweeps_fast(), keep this loop written out with the same rule: they add the
+// cross rows' badc, the hand-over to a structure loop and the priority raise, and with sweeps() on a skeleton
+// with hooks for those the fp64 latency reset kernel spilled 36 registers instead of 28.)
+template <class Rows>
+CP_DEV void sweep_loop(Ctx& c, int it0, int it1, Stamps& ST, Rows&& rows) {
+    (void)ST;
     for (int it = it0; it < it1; ++it) {
         if (__ballot(c.active) == 0ull) break;
 #ifdef CP_STAMPS
         ST.sweeps += 1;
 #endif
         bool bad = false;
-        if (c.active) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                bad |= fast_grow_ez<0, false>(c.I.d1, c.I.im1, F.g0[k].rbt, F.g0[k].ib, F.g0[k].ie, F.g0[k].tg,
-                                              F.g0[k].lam, real(0.0), tol);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) bad |= fast_crow(c.I, n2, F.c2[k], F.c2[k].lam, tol);
-        }
-        const uint32_t pbad = partner_u(bad ? 1u : 0u);  // every lane that entered the loop is here
+        if (c.active) bad = rows();
+        const uint32_t pbad = partner_u(bad ? 1u : 0u);
         if (c.active && !bad && pbad == 0u) c.active = false;
     }
 }
 
-// The bump phase's structures: the cart on the ground (4 rows of local pair 0, normal exactly +z) and
-// 0-4 rows of its pole on the cart (a tilting or bouncing pole), no pole-ground rows, no cross contact.
-// ~94 % of the island-substeps of a reset's 30 bump substeps that are not the settle structure
-// (oracle ORC_STATS run of 256 resets).
-CP_DEV bool c4k_ok(const Ctx& c) {
-    return pk_cnt(c.T.pk[0]) == 4 && pk_cnt(c.T.pk[1]) == 0 && !c.merged && is_plus_z(c.T.n[0]) &&
-           pk_fcnt(c.T.pk[0]) == 0 && pk_fcnt(c.T.pk[2]) == 0;
-}
-
-// sweeps_c44 with the cart-pole rows guarded by the lane's own count (the same rows in the same order
-// as sweeps_fast runs them for this structure, without its other pairs' guards and checks)
-template <class FI>
-CP_DEV void sweeps_c4k(Ctx& c, FI& F, real tol, int it0, int it1, Stamps& ST) {
+// ---- the structure loops: every active lane of the wave in one row structure -> that structure's rows in
+// the general loops' order, straight-line, without their per-row lane guards, +z tests and cross blocks.
+// c44_ok (EXACT) / c4k_ok: 4 ground-cart rows in +z form, then the cart-pole rows (EXACT: all 4, else
+// guarded by the lane's own count), fast form
+template <bool EXACT, class FI>
+CP_DEV void sweeps_c4(Ctx& c, FI& F, real tol, int it0, int it1, Stamps& ST) {
     const V3 n2 = c.T.n[2];
     const int cnt2 = pk_cnt(c.T.pk[2]);
-    for (int it = it0; it < it1; ++it) {
-        if (__ballot(c.active) == 0ull) break;
-#ifdef CP_STAMPS
-        ST.sweeps += 1;
-#endif
+    sweep_loop(c, it0, it1, ST, [&] {
         bool bad = false;
-        if (c.active) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                bad |= fast_grow_ez<0, false>(c.I.d1, c.I.im1, F.g0[k].rbt, F.g0[k].ib, F.g0[k].ie, F.g0[k].tg,
-                                              F.g0[k].lam, real(0.0), tol);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < cnt2) bad |= fast_crow(c.I, n2, F.c2[k], F.c2[k].lam, tol);
-        }
-        const uint32_t pbad = partner_u(bad ? 1u : 0u);  // every lane that entered the loop is here
-        if (c.active && !bad && pbad == 0u) c.active = false;
-    }
+        ground_rows_ez(F.g0, c.I.d1, c.I.im1, tol, bad);
+        cart_pole_rows<EXACT>(F.c2, c.I, n2, tol, bad, cnt2);
+        return bad;
+    });
 }
 
-// the p1_ok island's rows (pole on the ground) in fast form, guard-free (the lean step loops)
+// p1_ok (pole on the ground) in fast form (the lean step loops): the cart's 0 or 4 ground rows, the pole's 4,
+// its 4 friction points
 template <class FI>
 CP_DEV void sweeps_p1_fast(Ctx& c, FI& F, real tol, int it0, int it1, Stamps& ST) {
     const bool cart = pk_cnt(c.T.pk[0]) != 0;
-    for (int it = it0; it < it1; ++it) {
-        if (__ballot(c.active) == 0ull) break;
-#ifdef CP_STAMPS
-        ST.sweeps += 1;
-#endif
+    sweep_loop(c, it0, it1, ST, [&] {
         bool bad = false;
-        if (c.active) {
-            if (cart) {
+        if (cart) ground_rows_ez(F.g0, c.I.d1, c.I.im1, tol, bad);
+        ground_rows_ez(F.g1, c.I.d2, c.I.im2, tol, bad);
+        // the pole's 4 friction points, written out: as a row group the residual flags were or-ed in one serial
+        // chain (same instruction count, WIDE step kernel at B = 1 45.5 -> 45.7 us)
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    bad |= fast_grow_ez<0, false>(c.I.d1, c.I.im1, F.g0[k].rbt, F.g0[k].ib, F.g0[k].ie, F.g0[k].tg,
-                                                  F.g0[k].lam, real(0.0), tol);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                bad |= fast_grow_ez<0, false>(c.I.d2, c.I.im2, F.g1[k].rbt, F.g1[k].ib, F.g1[k].ie, F.g1[k].tg,
-                                              F.g1[k].lam, real(0.0), tol);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const real bound = c.mu1 * F.g1[k].lam;
-                bad |= fast_grow_ez<1, true>(c.I.d2, c.I.im2, F.f1[k].rbt1, F.f1[k].ib1, F.f1[k].ie1, real(0.0),
-                                             F.f1[k].l1, bound, tol);
-                bad |= fast_grow_ez<2, true>(c.I.d2, c.I.im2, F.f1[k].rbt2, F.f1[k].ib2, F.f1[k].ie2, real(0.0),
-                                             F.f1[k].l2, bound, tol);
-            }
+        for (int k = 0; k < 4; ++k) {
+            const real bound = c.mu1 * F.g1[k].lam;
+            bad |= fast_grow_ez<1, true>(c.I.d2, c.I.im2, F.f1[k].rbt1, F.f1[k].ib1, F.f1[k].ie1, real(0.0),
+                                         F.f1[k].l1, bound, tol);
+            bad |= fast_grow_ez<2, true>(c.I.d2, c.I.im2, F.f1[k].rbt2, F.f1[k].ib2, F.f1[k].ie2, real(0.0),
+                                         F.f1[k].l2, bound, tol);
         }
-        const uint32_t pbad = partner_u(bad ? 1u : 0u);  // every lane that entered the loop is here
-        if (c.active && !bad && pbad == 0u) c.active = false;
-    }
+        return bad;
+    });
 }
 
-// sweeps() when every active lane of the wave has the settle structure, rows from the LDS
-// pool: then the ground-cart rows are pool slots 0-3 and the cart-pole rows slots 4-7 on every
-// lane (the pool fills in pair order), so the loop is straight-line with compile-time slots.
-CP_DEV void sweeps_c44_slow(Ctx& c, real* pool, real tol, int it0, int it1, Stamps& ST) {
-    const V3 n2 = c.T.n[2];
-    for (int it = it0; it < it1; ++it) {
-        if (__ballot(c.active) == 0ull) break;
-#ifdef CP_STAMPS
-        ST.sweeps += 1;
-#endif
-        bool bad = false;
-        if (c.active) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const V3 rb = mk(pool_n(pool, F_RBX, s), pool_n(pool, F_RBY, s), pool_n(pool, F_RBZ, s));
-                real lam = pool_n(pool, F_LAM, s);
-                bad |= isl_row_ez<1, 0, false>(c.I, rb, pool_n(pool, F_IE, s), pool_n(pool, F_TG, s), lam, real(0.0),
-                                               tol);
-                pool_n(pool, F_LAM, s) = lam;
-            }
-#pragma unroll
-            for (int s = 4; s < 8; ++s) {
-                const V3 rb = mk(pool_n(pool, F_RBX, s), pool_n(pool, F_RBY, s), pool_n(pool, F_RBZ, s));
-                real lam = pool_n(pool, F_LAM, s);
-                bad |= isl_row<1, 2, false>(c.I, rb, n2, pool_n(pool, F_IE, s), pool_n(pool, F_TG, s), lam, real(0.0),
-                                            tol);
-                pool_n(pool, F_LAM, s) = lam;
-            }
-        }
-        const uint32_t pbad = partner_u(bad ? 1u : 0u);  // every lane that entered the loop is here
-        if (c.active && !bad && pbad == 0u) c.active = false;
-    }
-}
-
-// sweeps_c44_slow for the bump phase's structures (c4k_ok): the cart-pole rows are pool slots 4 .. 4 +
-// the lane's count - 1 (local pair 1 has no rows), guarded by that count
-CP_DEV void sweeps_c4k_slow(Ctx& c, real* pool, real tol, int it0, int it1, Stamps& ST) {
+// sweeps_c4 with the rows from the LDS pool (handed over by sweeps()): the pool fills in pair order and local
+// pair 1 has no rows, so on every lane the ground-cart rows are pool slots 0-3 and the cart-pole rows slots 4-7
+// (EXACT) or 4 .. 4 + the lane's count - 1: compile-time slots
+template <bool EXACT>
+CP_DEV void sweeps_c4_slow(Ctx& c, real* pool, real tol, int it0, int it1, Stamps& ST) {
     const V3 n2 = c.T.n[2];
     const int cnt2 = pk_cnt(c.T.pk[2]);
-    for (int it = it0; it < it1; ++it) {
+    sweep_loop(c, it0, it1, ST, [&] {
+        bool bad = false;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) pool_row_ez<1>(c.I, pool, s, tol, bad);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (EXACT || k < cnt2) pool_row<1, 2>(c.I, pool, 4 + k, n2, tol, bad);
+        return bad;
+    });
+}
+
+// ---- the general loops: any mix of structures in the wave.  Row order of a sweep: ground-cart, ground-pole,
+// cart-pole normals, cross normals, then the frictions in the same order, cross frictions.
+// Rows from the LDS pool.  HX = false: no env of the wave is merged (checked by the caller), so the cross-row
+// blocks and the merge of their results into the island view are compiled out of the sweep
+template <bool C44 = false, bool PM = false, bool HX = true>
+CP_DEV void sweeps(Ctx& c, Sim& S, const cp_physics& P, real* pool, real* pool0, bool second, int it0, int it1,
+                   Stamps& ST) {
+    const real tol = sqrt_(real(P.residual_threshold));  // oracle: SQRT((real)threshold)
+    // the ground-pole pair's tangent basis (with the URDF frictions the only island pair with
+    // friction rows: the carts' friction is 0), once per substep instead of once per sweep:
+    // step kernel 0.772 -> 0.753 ms
+    V3 h1 = mk(real(0.0), real(0.0), real(0.0)), h2 = h1;
+    if constexpr (!PM) plane_space(c.T.n[1], h1, h2);
+    // ground pairs whose rows all have a +z normal in this wave run isl_row_ez (wave-uniform):
+    // the ground-pole pair in every measured wave, the ground-cart pair in ~3 of 4 (PM: every row
+    // has its own normal, the generic rows)
+    const bool ez0 = !PM && __ballot(pk_cnt(c.T.pk[0]) > 0 && !is_plus_z(c.T.n[0])) == 0ull;
+    const bool ez1 = !PM && __ballot(pk_cnt(c.T.pk[1]) > 0 && !is_plus_z(c.T.n[1])) == 0ull;
+#ifdef CP_STAMPS
+    ST.flags |= (ez0 ? 0u : 2u) | (ez1 ? 0u : 4u);
+#endif
+    for (int it = it0; it < it1; ++it) {  // sweep_loop's stopping rule, + the cross rows' badc
         if (__ballot(c.active) == 0ull) break;
+        // a wave deep into a long solve (a capped env: the launch's tail) takes its SIMD's issue
+        // priority from its co-resident partner: C3 +1.2 % (threshold 8, 16 or 30 alike)
+        if constexpr (!C44) {
+            if (it == it0 + kPrioAfter) {
+                __builtin_amdgcn_s_setprio(1);
+            }
+        }
+        if constexpr (C44 && !PM) {  // every still-active lane in the settle structure (the reset kernels)
+            if ((it - it0) % kC44Check == 0 && __ballot(c.active && !c44_ok(c)) == 0ull) {
+                sweeps_c4_slow<true>(c, pool, tol, it, it1, ST);
+                return;
+            }
+            if (it == it0 && __ballot(c.active && !c4k_ok(c)) == 0ull) {  // the bump phase's structures
+                sweeps_c4_slow<false>(c, pool, tol, it, it1, ST);
+                return;
+            }
+        }
 #ifdef CP_STAMPS
         ST.sweeps += 1;
 #endif
-        bool bad = false;
+        bool bad = false, badc = false;
         if (c.active) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const V3 rb = mk(pool_n(pool, F_RBX, s), pool_n(pool, F_RBY, s), pool_n(pool, F_RBZ, s));
-                real lam = pool_n(pool, F_LAM, s);
-                bad |= isl_row_ez<1, 0, false>(c.I, rb, pool_n(pool, F_IE, s), pool_n(pool, F_TG, s), lam, real(0.0),
-                                               tol);
-                pool_n(pool, F_LAM, s) = lam;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (k < cnt2) {
-                    const int s = 4 + k;
-                    const V3 rb = mk(pool_n(pool, F_RBX, s), pool_n(pool, F_RBY, s), pool_n(pool, F_RBZ, s));
-                    real lam = pool_n(pool, F_LAM, s);
-                    bad |= isl_row<1, 2, false>(c.I, rb, n2, pool_n(pool, F_IE, s), pool_n(pool, F_TG, s), lam,
-                                                real(0.0), tol);
-                    pool_n(pool, F_LAM, s) = lam;
-                }
-            }
+            if (ez0) isl_normal_rows_ez<0>(c.I, c.T, pool, tol, bad);
+            else isl_normal_rows<0, PM>(c.I, c.T, pool, tol, bad);
+            if (ez1) isl_normal_rows_ez<1>(c.I, c.T, pool, tol, bad);
+            else isl_normal_rows<1, PM>(c.I, c.T, pool, tol, bad);
+            isl_normal_rows<2, PM>(c.I, c.T, pool, tol, bad);
         }
-        const uint32_t pbad = partner_u(bad ? 1u : 0u);  // every lane that entered the loop is here
-        if (c.active && !bad && pbad == 0u) c.active = false;
+        const bool cross = HX && c.active && c.merged;  // same on both lanes of an env
+        if (HX && __ballot(cross) != 0ull && cross) cross_rows<X_NORMAL, PM>(S, c, second, P, pool0, tol, badc);
+        if (c.active) {
+            if (ez0) isl_friction_rows_ez<0>(c.I, c.T, c.mu0, pool, tol, bad);
+            else isl_friction_rows<0, false, PM>(c.I, c.T, c.mu0, pool, tol, bad);
+            if (ez1) isl_friction_rows_ez<1>(c.I, c.T, c.mu1, pool, tol, bad);
+            else if (PM) isl_friction_rows<1, false, PM>(c.I, c.T, c.mu1, pool, tol, bad);
+            else isl_friction_rows<1, true>(c.I, c.T, c.mu1, pool, tol, bad, h1, h2);
+            isl_friction_rows<2, false, PM>(c.I, c.T, c.mu2, pool, tol, bad);
+        }
+        // the friction half only where a cross pair has friction rows: cross_view + cross_back alone
+        // change no value (the whole-env view and back), and a wave with a merged env pays them per sweep
+        const bool crossf = cross && c.xfric;
+        if (HX && __ballot(crossf) != 0ull && crossf) cross_rows<X_FRICTION, PM>(S, c, second, P, pool0, tol, badc);
+        // every lane that entered the loop is here (pairs together): the env's joint decision
+        const uint32_t pbad = partner_u(bad ? 1u : 0u);
+        if (c.active && !bad && !badc && pbad == 0u) c.active = false;
     }
+    if constexpr (!C44) __builtin_amdgcn_s_setprio(0);
 }
-
-// The step kernels' dominant island (tools/row_classes.py: 94 % of the C3 steady state's island
-// solves, and nearly all of the sweep-cap stragglers): the pole standing on the ground on its 1 cm
-// base (local pair 1: 4 normal rows and 4 friction points, normal exactly +z), its cart either off
-// the ground or standing on it (local pair 0: 0 or 4 rows, +z), nothing on the cart-pole pair, no
-// friction rows on pairs 0 / 2, no cross contact.
-CP_DEV bool p1_ok(const Ctx& c) {
-    const int c0 = pk_cnt(c.T.pk[0]);
-    return pk_cnt(c.T.pk[1]) == 4 && pk_fcnt(c.T.pk[1]) == 4 && is_plus_z(c.T.n[1]) && pk_cnt(c.T.pk[2]) == 0 &&
-           pk_fcnt(c.T.pk[0]) == 0 && pk_fcnt(c.T.pk[2]) == 0 && !c.merged &&
-           (c0 == 0 || (c0 == 4 && is_plus_z(c.T.n[0])));
-}
-
 
 // sweeps() with the island rows in fast form (same row order, same stopping rule)
 template <bool C44, bool HC2, bool HX = true>
@@ -1682,11 +1653,11 @@ CP_DEV void sweeps_fast(Ctx& c, FastIslT<HC2>& F, Sim& S, const cp_physics& P, r
         if constexpr (C44 && HC2) {
             if ((it - it0) % kC44Check == 0 && __ballot(c.active && !c44_ok(c)) == 0ull) {
                 CP_STAMP(q0);
-                sweeps_c44(c, F, tol, it, it1, ST);
+                sweeps_c4<true>(c, F, tol, it, it1, ST);
                 return;
             }
             if (it == it0 && __ballot(c.active && !c4k_ok(c)) == 0ull) {  // the bump phase's structures
-                sweeps_c4k(c, F, tol, it, it1, ST);
+                sweeps_c4<false>(c, F, tol, it, it1, ST);
                 return;
             }
         }
@@ -1724,12 +1695,7 @@ CP_DEV void sweeps_fast(Ctx& c, FastIslT<HC2>& F, Sim& S, const cp_physics& P, r
         }
         const bool cross = HX && c.active && c.merged;  // same on both lanes of an env
         if (HX && __ballot(cross) != 0ull && cross) {
-            cross_view(S, c.T, c.I, second);
-            pair_normal_rows<5>(S, c.T, second, P, pool0, tol, badc);
-            pair_normal_rows<6>(S, c.T, second, P, pool0, tol, badc);
-            pair_normal_rows<7>(S, c.T, second, P, pool0, tol, badc);
-            pair_normal_rows<8>(S, c.T, second, P, pool0, tol, badc);
-            cross_back(c.I, S, second);
+            cross_rows<X_NORMAL>(S, c, second, P, pool0, tol, badc);
         }
         if (c.active) {
             if (ez1) {
@@ -1758,37 +1724,17 @@ CP_DEV void sweeps_fast(Ctx& c, FastIslT<HC2>& F, Sim& S, const cp_physics& P, r
         }
         const bool crossf = cross && c.xfric;  // see sweeps()
         if (HX && __ballot(crossf) != 0ull && crossf) {
-            cross_view(S, c.T, c.I, second);
-            pair_friction_rows<5>(S, c.T, second, P, pool0, tol, badc);
-            pair_friction_rows<6>(S, c.T, second, P, pool0, tol, badc);
-            pair_friction_rows<7>(S, c.T, second, P, pool0, tol, badc);
-            pair_friction_rows<8>(S, c.T, second, P, pool0, tol, badc);
-            cross_back(c.I, S, second);
+            cross_rows<X_FRICTION>(S, c, second, P, pool0, tol, badc);
         }
         const uint32_t pbad = partner_u(bad ? 1u : 0u);  // every lane that entered the loop is here
         if (c.active && !bad && !badc && pbad == 0u) c.active = false;
     }
 }
 
-// the island rows' impulses back into the pool (substep_finish refreshes the
-// warm-start cache from it)
-template <bool HC2>
-CP_DEV void fast_store(const FastIslT<HC2>& F, const Ctx& c, real* pool) {
-    const int cnt0 = pk_cnt(c.T.pk[0]), cnt1 = pk_cnt(c.T.pk[1]), cnt2 = pk_cnt(c.T.pk[2]);
-    const int b0 = pk_base(c.T.pk[0]), b1 = pk_base(c.T.pk[1]), b2 = pk_base(c.T.pk[2]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (k < cnt0) pool_n(pool, F_LAM, b0 + k) = F.g0[k].lam;
-        if (k < cnt1) pool_n(pool, F_LAM, b1 + k) = F.g1[k].lam;
-        if constexpr (HC2)
-            if (k < cnt2) pool_n(pool, F_LAM, b2 + k) = F.c2[k].lam;
-    }
-}
-
 // The lean structure loops: every active lane of the wave in one of the common row structures at the first
 // sweep -> only that structure's rows in fast form (FastC4, FastP1: ~100-120 values, no AGPR moves in the
 // latency kernels) and its guard-free loop, the same rows in the same order as the general loops.
-//   c4k_ok (FastC4, sweeps_c44 / sweeps_c4k): the cart on the ground and 0-4 rows of its pole standing on it:
+//   c4k_ok (FastC4, sweeps_c4): the cart on the ground and 0-4 rows of its pole standing on it:
 //     every island of a reset's settle substeps, ~99 % of the bump substeps', a step's first substeps;
 //   p1_ok (FastP1, sweeps_p1_fast, step kernels): the pole lying or standing on the ground (93-98 % of the
 //     islands from step 26 of an episode on).
@@ -1816,9 +1762,9 @@ CP_DEV bool solve_lean(Ctx& c, const cp_physics& P, real* pool, int it0, int it1
             fast_ground_rows<0>(F.g0, c, pool);
             fast_cart_pole_rows(F.c2, c, pool);
             if (__ballot(c.active && !c44_ok(c)) == 0ull)
-                run([&](int a, int b) { sweeps_c44(c, F, tol, a, b, ST); });
+                run([&](int a, int b) { sweeps_c4<true>(c, F, tol, a, b, ST); });
             else
-                run([&](int a, int b) { sweeps_c4k(c, F, tol, a, b, ST); });
+                run([&](int a, int b) { sweeps_c4<false>(c, F, tol, a, b, ST); });
             const int b0 = pk_base(c.T.pk[0]), cnt2 = pk_cnt(c.T.pk[2]), b2 = pk_base(c.T.pk[2]);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {  // fast_store (c4k_ok: 4 rows on pair 0, none on pair 1)
@@ -2579,10 +2525,8 @@ CP_DEV void substep_prep(Own& O, Sim& X, const cp_physics& P, const Lane& L, rea
     isl_warmstart<1, PM>(I, T, pool);
     isl_warmstart<2, PM>(I, T, pool);
     if (__ballot(c.merged) != 0ull && c.merged) {
-        cross_view(X, T, I, second);
-        pair_warmstart<5, PM>(X, T, second, P, pool0); pair_warmstart<6, PM>(X, T, second, P, pool0);
-        pair_warmstart<7, PM>(X, T, second, P, pool0); pair_warmstart<8, PM>(X, T, second, P, pool0);
-        cross_back(I, X, second);
+        bool none = false;
+        cross_rows<X_WARM, PM>(X, c, second, P, pool0, real(0.0), none);
     }
     c.active = c.tot > 0;  // same on both lanes of the env
 }
@@ -2698,7 +2642,7 @@ CP_DEV const cp_physics& fresh_phys(const cp_physics& P) {
 // One p.stepSimulation() for this lane's env.
 // FAST: fast-form island rows where the wave allows them (the 512-register kernels);
 // C44: the latency-shaped reset kernel's options: the guard-free settle-structure loop
-// (sweeps_c44) and the all-inside face-contact exit (face_contact<ALLIN>).
+// (sweeps_c4) and the all-inside face-contact exit (face_contact<ALLIN>).
 // PM: CP_MODEL_PERSISTENT (Bullet's persistent manifold, per-row normals in the pool).
 // SLP: CP_MODEL_SLEEPING (Bullet's deactivation: sleeping islands are neither integrated nor solved).
 template <bool FAST = false, bool C44 = false, bool ALLIN = C44, bool PM = false, bool SLP = false, int WIDE = 0>

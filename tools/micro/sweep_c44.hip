@@ -1,5 +1,5 @@
 // Microbenchmark (diagnostic, not part of the library): the latency-shaped kernels' settle-structure PGS
-// sweep (cp_physics.h sweeps_c44: 4 +z ground rows, then 4 cart-pole rows, fast form) run by one wave
+// sweep (cp_physics.h sweeps_c4<true>: 4 +z ground rows, then 4 cart-pole rows, fast form) run by one wave
 // alone on its SIMD, on synthetic rows; cycles per sweep (s_memtime) vs the same wave count spread.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -DCP_STAMPS \
 //     -mllvm -amdgpu-sched-strategy=iterative-ilp tools/micro/sweep_c44.hip -o tools/micro/sweep_c44
@@ -38,7 +38,7 @@ bench_c44(const float* in, float* out, unsigned long long* cyc, int nsweeps) {
     }
     c.active = true;
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    sweeps_c44(c, F, 0.0f, 0, nsweeps, ST);
+    sweeps_c4<true>(c, F, 0.0f, 0, nsweeps, ST);
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
     float acc = c.I.d1.v.x + c.I.d1.w.y + c.I.d2.v.z + c.I.d2.w.x;
     for (int r = 0; r < 4; ++r) acc += F.g0[r].lam + F.c2[r].lam;
