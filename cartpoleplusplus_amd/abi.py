@@ -5,7 +5,7 @@ library's entry points with these types.
 """
 import ctypes as C
 
-CP_ABI_VERSION = 7
+CP_ABI_VERSION = 8
 
 CP_BODY_GROUND, CP_BODY_CART, CP_BODY_POLE, CP_BODY_CART2, CP_BODY_POLE2 = range(5)
 CP_NUM_BODIES = 5
@@ -181,6 +181,8 @@ class cp_policy(C.Structure):
         ("epsilon", C.c_float),
         ("seed", C.c_uint64),
         ("weights", C.c_void_p),
+        ("population", C.c_int32),
+        ("group", C.c_int32),
     ]
 
 

@@ -281,18 +281,30 @@ class BatchedCartpole:
                                                  float(done_pos), float(done_angle)), "cp_set_lqr")
 
     # ------------------------------------------------- in-kernel MLP policy
-    def set_policy(self, layers, head="tanh", epsilon=0.0, seed=0):
+    def set_policy(self, layers, head="tanh", epsilon=0.0, seed=0, group=None):
         """Dense ReLU MLP policy for policy_act() (cp_set_policy): layers is a list of
         (W, b) tensors or an nn.Sequential of Linear / ReLU, head "tanh" / "clip" (continuous, 4 outputs)
         or "argmax" / "sample" (discrete, 2 x 5 logits; epsilon, seed for "sample").  None turns it off.
         self.policy_weights is the packed device tensor the kernels read at every launch: new weights
-        written into it in place (policy.repack) take effect at the next launch."""
+        written into it in place (policy.repack) take effect at the next launch.
+
+        A population: a list / tuple of modules, or `group` given (then layers is whatever
+        policy.pack_population takes), puts P networks of one architecture behind the handle; env i reads
+        member ((env_id_offset + i) // group) % P, group defaulting to ceil(B / P) (P equal blocks of a
+        single handle).  self.policy_weights is then the (P, F) tensor, one packed row per member."""
         from . import policy
         if layers is None:
             native.check(self.h, self.lib.cp_set_policy(self.h, None), "cp_set_policy")
             self.policy_weights = self.policy = None
             return None
-        packed, pol = policy.pack(layers, head, epsilon=epsilon, seed=seed, device=self.device)
+        modules = isinstance(layers, (list, tuple)) and len(layers) > 0 and all(
+            isinstance(m, torch.nn.Module) for m in layers)
+        if modules or group is not None:
+            if group is None:
+                group = -(-self.B // len(layers))
+            packed, pol = policy.pack_population(layers, head, group, epsilon=epsilon, seed=seed, device=self.device)
+        else:
+            packed, pol = policy.pack(layers, head, epsilon=epsilon, seed=seed, device=self.device)
         native.check(self.h, self.lib.cp_set_policy(self.h, C.byref(pol)), "cp_set_policy")
         self.policy_weights, self.policy = packed, pol
         return packed

@@ -142,6 +142,10 @@ struct Pol {
     const float* obs_in;   // [B][R][2][7] the obs to act on
     const float* noise;    // [B][2][2] or null
     void* actions_out;     // [B][2][2] f32 or [B][2] i8
+    // populations (appended: the fields above keep their kernel-argument offsets)
+    int32_t population;    // P weight sets [P][floats]; <= 1: one policy for all envs
+    int32_t group;         // G consecutive global env ids per member (population > 1)
+    int64_t floats;        // F: one member's weight floats
 };
 
 // Per-handle device buffers.  `state` and `scratch` hold the handle's real type.
@@ -196,5 +200,5 @@ CP_DECLARE_LAUNCHES(cp)
 CP_DECLARE_LAUNCHES(cp64)
 // the MLP policy's kernels exist in fp32 only (cp_kernels.hip defines CP_POLICY)
 namespace cp {
-void launch_policy_act(int kind, const cp_config& cfg, const cpc::Bufs& b, const cpc::Pol& pol, hipStream_t st);
+hipError_t launch_policy_act(int kind, const cp_config& cfg, const cpc::Bufs& b, const cpc::Pol& pol, hipStream_t st);
 }

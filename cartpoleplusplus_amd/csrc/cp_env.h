@@ -974,12 +974,34 @@ void launch_rollout(int shape, int kind, const cp_config& cfg, const Bufs& b, in
 }
 
 #ifdef CP_POLICY  // the fp32 translation unit only
-void launch_policy_act(int kind, const cp_config& cfg, const Bufs& b, const cpc::Pol& pol, hipStream_t st) {
-    const dim3 grid(env_grid(cfg.num_envs, WAVE)), block(WAVE);  // one lane per env
-    if (kind == CP_ACTION_CONTINUOUS)
-        hipLaunchKernelGGL(cp_policy_act_kernel<CP_ACTION_CONTINUOUS>, grid, block, 0, st, cfg, b, pol);
-    else
-        hipLaunchKernelGGL(cp_policy_act_kernel<CP_ACTION_DISCRETE>, grid, block, 0, st, cfg, b, pol);
+// cp_policy_act's kernel by cps::policy_path: the lane-per-env kernel (one weight set, or one member per wave), or
+// one member run's chunk per wave with the chunk's tiles and a layer's weights in dynamic LDS
+hipError_t launch_policy_act(int kind, const cp_config& cfg, const Bufs& b, const cpc::Pol& pol, hipStream_t st) {
+    const cps::PolicyPath path = cps::policy_path(pol.population, pol.group, cfg.env_id_offset);
+    const dim3 block(WAVE);
+    auto by_kind = [&](auto cont, auto disc, dim3 grid, size_t lds, auto... args) {
+        if (kind == CP_ACTION_CONTINUOUS) hipLaunchKernelGGL(cont, grid, block, lds, st, cfg, b, pol, args...);
+        else hipLaunchKernelGGL(disc, grid, block, lds, st, cfg, b, pol, args...);
+    };
+    if (path == cps::POLICY_MEMBER) {
+        const cps::PolicyRuns runs = cps::policy_runs(cfg.env_id_offset, pol.group, cfg.num_envs);
+        const size_t lds = cps::policy_member_lds_bytes(pol.width, pol.num_layers, pol.group, cfg.num_envs);
+        if (lds > 64 * 1024) {  // above the default dynamic-LDS limit (widest layers with 64-env chunks: 136 KiB)
+            const void* f = kind == CP_ACTION_CONTINUOUS ? (const void*)cp_policy_member_kernel<CP_ACTION_CONTINUOUS>
+                                                         : (const void*)cp_policy_member_kernel<CP_ACTION_DISCRETE>;
+            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        by_kind(cp_policy_member_kernel<CP_ACTION_CONTINUOUS>, cp_policy_member_kernel<CP_ACTION_DISCRETE>,
+                dim3((unsigned)runs.runs * (unsigned)runs.chunks_per_run), lds, runs);
+    } else if (path == cps::POLICY_WAVE) {
+        by_kind(cp_policy_act_kernel<CP_ACTION_CONTINUOUS, true>, cp_policy_act_kernel<CP_ACTION_DISCRETE, true>,
+                dim3(env_grid(cfg.num_envs, WAVE)), 0);
+    } else {
+        by_kind(cp_policy_act_kernel<CP_ACTION_CONTINUOUS, false>, cp_policy_act_kernel<CP_ACTION_DISCRETE, false>,
+                dim3(env_grid(cfg.num_envs, WAVE)), 0);
+    }
+    return hipSuccess;
 }
 #endif  // CP_POLICY
 

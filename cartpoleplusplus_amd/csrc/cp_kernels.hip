@@ -717,6 +717,9 @@ static int64_t policy_floats(cp_handle* h, const cp_policy* p, const char* who) 
         return fail(h, w + "the head's out width must be " + std::to_string(out) +
                            (out == 4 ? " (continuous: a00 a01 a10 a11)" : " (discrete: 2 carts x 5 logits)"));
     if (!(p->epsilon >= 0.0f && p->epsilon <= 1.0f)) return fail(h, w + "epsilon must be in [0, 1]");
+    if (p->population < 0) return fail(h, w + "population must be >= 0 (0 or 1: one policy for all envs)");
+    if (p->population > 1 && p->group < 1)
+        return fail(h, w + "group must be >= 1 with a population (consecutive global env ids per member)");
     int64_t n = 0;
     for (int l = 0; l < p->num_layers; ++l) n += (int64_t)p->width[l + 1] * (p->width[l] + 1);
     return n;
@@ -730,7 +733,8 @@ int cp_set_policy(cp_handle* h, const cp_policy* p) {
         h->pol_on = false;
         return 0;
     }
-    if (policy_floats(h, p, "cp_set_policy") < 0) return -1;
+    const int64_t floats = policy_floats(h, p, "cp_set_policy");
+    if (floats < 0) return -1;
     if (h->f64) return fail(h, "cp_set_policy: the MLP policy is fp32 only (not for CP_PRECISION_F64 handles)");
     if (h->cfg.phys.model_flags & (CP_MODEL_PERSISTENT | CP_MODEL_SLEEPING))
         return fail(h, "cp_set_policy: not built for CP_MODEL_PERSISTENT / CP_MODEL_SLEEPING handles");
@@ -741,6 +745,8 @@ int cp_set_policy(cp_handle* h, const cp_policy* p) {
         return fail(h, "cp_set_policy: width[0] must be 14 * action_repeats = " + std::to_string(14 * h->cfg.action_repeats) +
                            " (the obs [R][2][7] flattened)");
     if (!p->weights) return fail(h, "cp_set_policy: null weights");
+    if (p->population > 1 && h->cfg.env_id_offset < 0)
+        return fail(h, "cp_set_policy: a population needs env_id_offset >= 0 (the member is (global id / group) % population)");
     if ((unsigned long long)h->cfg.num_envs * 2ull * CP_POLICY_MAX_WIDTH * sizeof(float) >= (1ull << 32))
         return fail(h, "cp_set_policy: num_envs too large (the activation scratch SoA must stay below 4 GiB)");
     if (!h->pol.scratch) {
@@ -753,6 +759,9 @@ int cp_set_policy(cp_handle* h, const cp_policy* p) {
     h->pol.epsilon = p->epsilon;
     h->pol.seed = p->seed;
     h->pol.weights = p->weights;
+    h->pol.population = p->population;
+    h->pol.group = p->group;
+    h->pol.floats = floats;
     h->pol_on = true;
     return 0;
 }
@@ -770,7 +779,7 @@ int cp_policy_act(cp_handle* h, const float* obs, const float* noise, void* acti
     pol.obs_in = obs;
     pol.noise = noise;
     pol.actions_out = actions_out;
-    cp::launch_policy_act(policy_kind(h), h->cfg, h->b, pol, st);
+    CP_TRY(h, cp::launch_policy_act(policy_kind(h), h->cfg, h->b, pol, st));
     CP_TRY(h, hipGetLastError());
     return 0;
 }

@@ -1,6 +1,7 @@
 // cp_policy.h — the in-kernel dense ReLU MLP policy (cp_set_policy): the agents'
 // observation -> small MLP -> action (lrpg_cartpole.py:149-163, ddpg_cartpole.py:121-138), evaluated by
-// one lane per env by cp_policy_act_kernel.  fp32 only; included by cp_env.h inside namespace CP_NS.
+// one lane per env by cp_policy_act_kernel, or, for a policy population whose members change inside a wave, by
+// one member run per wave (cp_policy_member_kernel, below).  fp32 only; included by cp_env.h inside namespace CP_NS.
 //
 // The arithmetic order is part of the C-ABI's contract (include/cartpole_amd.h): per unit acc = b[j], then
 // acc = fmaf(W[j][i], x[i], acc) for i ascending; hidden units max(acc, 0) as acc > 0 ? acc : 0.
@@ -36,10 +37,11 @@ CP_DEV void philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t
     w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
 }
 
-// The layers of the MLP over the lane's scratch column (coff = env * 4 bytes): the input x[0 .. width[0]) is
+// The layers of the MLP over the lane's scratch column (coff = env * 4 bytes), with the wave's weights woff
+// floats into p.weights (wave-uniform: 0, or the wave's member of a population): the input x[0 .. width[0]) is
 // in half 0; returns the half that holds the last layer's (linear) outputs.
-CP_DEV int policy_layers(const cpc::Pol& p, const SoaF& scr, uint32_t coff) {
-    PolW w = (PolW)(uintptr_t)p.weights;
+CP_DEV int policy_layers(const cpc::Pol& p, uint64_t woff, const SoaF& scr, uint32_t coff) {
+    PolW w = (PolW)(uintptr_t)(p.weights + woff);
     int half = 0;
     for (int l = 0; l < p.num_layers; ++l) {
         const int nin = p.width[l], nout = p.width[l + 1];
@@ -92,18 +94,17 @@ CP_DEV int policy_layers(const cpc::Pol& p, const SoaF& scr, uint32_t coff) {
     return half;
 }
 
-// One env's action from its obs row x[14 R] (unscaled), the caller's noise row (4 floats or null) and the
-// env's counters before the step: writes actions_out[row] (float4 or char2) and returns the unit action
-// a00 a01 a10 a11 the step scales by action_force.
-template <int KIND>
-CP_DEV void policy_act(const cpc::Pol& p, const SoaF& scr, uint32_t coff, const float* x, const float* noise, int steps,
-                       int episode, uint64_t gid, void* actions_out, size_t row, float a[4]) {
-    for (int i = 0; i < p.width[0]; ++i) scr.st(i, coff, x[i]);
-    const int zo = policy_layers(p, scr, coff) * CP_POLICY_MAX_WIDTH;
+// The head on one env's last-layer outputs zv(0 .. 3) (continuous) or zv(0 .. 9) (discrete; zv reads the z vector
+// where the kernel keeps it: the scratch column or the LDS tile), the caller's noise row (4 floats or null) and
+// the env's counters before the step: writes actions_out[row] (float4 or char2) and returns the unit action
+// a00 a01 a10 a11 the step scales by action_force.  Shared by both kernels.
+template <int KIND, typename Z>
+CP_DEV void policy_head(const cpc::Pol& p, const Z& zv, const float* noise, int steps, int episode, uint64_t gid,
+                        void* actions_out, size_t row, float a[4]) {
     if constexpr (KIND == CP_ACTION_CONTINUOUS) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            float z = scr.ld(zo + c, coff);
+            float z = zv(c);
             if (p.head == CP_HEAD_TANH) z = tanhf(z);
             a[c] = fminf(fmaxf(z + (noise ? noise[c] : 0.0f), -1.0f), 1.0f);
         }
@@ -114,7 +115,7 @@ CP_DEV void policy_act(const cpc::Pol& p, const SoaF& scr, uint32_t coff, const 
         for (int c = 0; c < 2; ++c) {
             float z[CP_NUM_DISCRETE];
 #pragma unroll
-            for (int j = 0; j < CP_NUM_DISCRETE; ++j) z[j] = scr.ld(zo + c * CP_NUM_DISCRETE + j, coff);
+            for (int j = 0; j < CP_NUM_DISCRETE; ++j) z[j] = zv(c * CP_NUM_DISCRETE + j);
             int best = 0;
             float m = z[0];
 #pragma unroll
@@ -160,9 +161,26 @@ CP_DEV void policy_act(const cpc::Pol& p, const SoaF& scr, uint32_t coff, const 
     }
 }
 
-// cp_policy_act: one lane per env, policy_act on the caller's obs and the state's
-// counters; an env that is done is not evaluated and gets a zero action.
+// One env's action from its obs row x[14 R] (unscaled) by the lane-per-env layers and the head.
 template <int KIND>
+CP_DEV void policy_act(const cpc::Pol& p, uint64_t woff, const SoaF& scr, uint32_t coff, const float* x, const float* noise,
+                       int steps, int episode, uint64_t gid, void* actions_out, size_t row, float a[4]) {
+    for (int i = 0; i < p.width[0]; ++i) scr.st(i, coff, x[i]);
+    const int zo = policy_layers(p, woff, scr, coff) * CP_POLICY_MAX_WIDTH;
+    policy_head<KIND>(p, [&](int j) { return scr.ld(zo + j, coff); }, noise, steps, episode, gid, actions_out, row, a);
+}
+
+template <int KIND>
+CP_DEV void policy_zero_action(void* actions_out, size_t row) {
+    if constexpr (KIND == CP_ACTION_CONTINUOUS) reinterpret_cast<float4*>(actions_out)[row] = make_float4(0.f, 0.f, 0.f, 0.f);
+    else reinterpret_cast<char2*>(actions_out)[row] = make_char2(0, 0);
+}
+
+// cp_policy_act, one lane per env: policy_act on the caller's obs and the state's counters; an env that is done
+// is not evaluated and gets a zero action.  POP (cps::POLICY_WAVE): a population whose members change at wave
+// boundaries only; the wave's member comes from the block index and kernel arguments, through readfirstlane, so
+// the weight base is wave-uniform to the compiler and the weight loads stay scalar.
+template <int KIND, bool POP>
 __global__ void __launch_bounds__(WAVE) cp_policy_act_kernel(cp_config cfg, Bufs b, cpc::Pol pol) {
     const int B = cfg.num_envs;
     const int i = blockIdx.x * WAVE + threadIdx.x;
@@ -171,13 +189,160 @@ __global__ void __launch_bounds__(WAVE) cp_policy_act_kernel(cp_config cfg, Bufs
     const uint32_t o = SoaT<float>::eoff(i);
     auto ldint = [&](int f) { return (int32_t)__float_as_uint(st.ld(f, o)); };
     if (ldint(CP_SF_DONE) != 0) {
-        if constexpr (KIND == CP_ACTION_CONTINUOUS) reinterpret_cast<float4*>(pol.actions_out)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        else reinterpret_cast<char2*>(pol.actions_out)[i] = make_char2(0, 0);
+        policy_zero_action<KIND>(pol.actions_out, (size_t)i);
         return;
+    }
+    uint64_t woff = 0;
+    if constexpr (POP) {
+        const uint64_t g0 = (uint64_t)cfg.env_id_offset + (uint64_t)blockIdx.x * WAVE;  // the wave's first global id
+        const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane(
+            (int)(uint32_t)((g0 / (uint32_t)pol.group) % (uint32_t)pol.population));
+        woff = (uint64_t)m * (uint64_t)pol.floats;  // added to the 64-bit base: member * F * 4 bytes passes 4 GiB
     }
     const SoaF scr = SoaF::make(pol.scratch, B, 2 * CP_POLICY_MAX_WIDTH);
     float a[4];
-    policy_act<KIND>(pol, scr, SoaF::eoff(i), pol.obs_in + (size_t)i * cfg.action_repeats * 14,
+    policy_act<KIND>(pol, woff, scr, SoaF::eoff(i), pol.obs_in + (size_t)i * cfg.action_repeats * 14,
                      pol.noise ? pol.noise + (size_t)i * 4 : nullptr, ldint(CP_SF_STEPS), ldint(CP_SF_EPISODE),
                      (uint64_t)(cfg.env_id_offset + i), pol.actions_out, (size_t)i, a);
+}
+
+// ---- the member path (cps::POLICY_MEMBER): one member run's chunk of n <= 64 envs per wave -------------------
+// A wave's lanes would belong to several members, so the lane-per-env kernel would read 64 weight sets per load.
+// Here the lanes are the layer's output units (two passes at widths above 64) and the chunk's envs are the loop:
+//   * the chunk's activations are two LDS tiles [unit][env] with env stride ES (cps::policy_env_stride), so the
+//     envs e0 .. e0+3 of one input unit are one 16-byte broadcast read;
+//   * a layer's W and b come from HBM once per chunk, as 16-byte loads over the contiguous [W | b] range (dword
+//     loads for the at most 6 floats before and after the 16-byte aligned part), into LDS at row stride nin | 1:
+//     lane j's read of W[j][i] then meets 32 distinct banks;
+//   * per (env, unit) acc = b[j] and the FMAs run i ascending, as in policy_layers: the same bits.
+// Element f of the [W | b] range lands at (f / nin) * stride + f % nin, the bias rows continuing W's grid.
+CP_DEV void member_stage_weights(const float* src, int nin, int nout, float* wl, int lane) {
+    const int stride = nin | 1, total = nout * nin + nout;
+    int head = (int)((0u - (uint32_t)((uintptr_t)src >> 2)) & 3u);  // floats up to the 16-byte boundary
+    head = head < total ? head : total;
+    const int nvec = (total - head) >> 2, tail0 = head + 4 * nvec;
+    if (lane < head + total - tail0) {
+        const int f = lane < head ? lane : tail0 + (lane - head);
+        const int j = f / nin;
+        wl[j * stride + (f - j * nin)] = src[f];
+    }
+    const float4* src4 = reinterpret_cast<const float4*>(src + head);
+    const int q = (4 * WAVE) / nin, r = 4 * WAVE - q * nin;  // a wave-wide load advances a lane by 256 floats
+    const int f0 = head + 4 * lane;
+    int j = f0 / nin, i = f0 - j * nin;
+    constexpr int U = 8;  // 16-byte loads in flight per lane before the LDS writes
+    for (int v0 = lane; v0 - lane < nvec; v0 += U * WAVE) {
+        float4 x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (v0 + u * WAVE < nvec) x[u] = src4[v0 + u * WAVE];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (v0 + u * WAVE < nvec) {
+                const float e[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
+                int jj = j, ii = i;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    wl[jj * stride + ii] = e[k];
+                    if (++ii >= nin) {
+                        ii = 0;
+                        ++jj;
+                    }
+                }
+            }
+            i += r;
+            j += q;
+            if (i >= nin) {
+                i -= nin;
+                ++j;
+            }
+        }
+    }
+}
+
+// Unit j's outputs for the envs e0 .. e0+E-1 of the chunk (columns past the chunk's last env hold don't-cares
+// inside the tile, computed and never read out)
+template <int E>
+CP_DEV void member_block(const float* wrow, float bias, const float* xs, float* out, int ES, int nin, bool hidden,
+                         bool store) {
+    float acc[E];
+#pragma unroll
+    for (int k = 0; k < E; ++k) acc[k] = bias;
+#pragma unroll 4
+    for (int i = 0; i < nin; ++i) {
+        const float w = wrow[i];
+#pragma unroll
+        for (int k = 0; k < E; k += 4) {
+            const float4 x = *reinterpret_cast<const float4*>(xs + i * ES + k);
+            acc[k + 0] = __builtin_fmaf(w, x.x, acc[k + 0]);
+            acc[k + 1] = __builtin_fmaf(w, x.y, acc[k + 1]);
+            acc[k + 2] = __builtin_fmaf(w, x.z, acc[k + 2]);
+            acc[k + 3] = __builtin_fmaf(w, x.w, acc[k + 3]);
+        }
+    }
+    if (!store) return;
+#pragma unroll
+    for (int k = 0; k < E; ++k)
+        if (hidden) acc[k] = acc[k] > 0.0f ? acc[k] : 0.0f;
+#pragma unroll
+    for (int k = 0; k < E; k += 4)
+        *reinterpret_cast<float4*>(out + k) = make_float4(acc[k], acc[k + 1], acc[k + 2], acc[k + 3]);
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(WAVE) cp_policy_member_kernel(cp_config cfg, Bufs b, cpc::Pol pol, cps::PolicyRuns runs) {
+    extern __shared__ float4 policy_lds[];
+    float* const lds = reinterpret_cast<float*>(policy_lds);
+    const int B = cfg.num_envs, lane = threadIdx.x;
+    const cps::PolicyChunk ch = cps::policy_chunk(cfg.env_id_offset, pol.group, pol.population, B, runs, (int)blockIdx.x);
+    const int n = ch.n, row = ch.lo + lane;
+    if (n <= 0) return;  // a short first or last run's trailing chunk (the whole wave leaves)
+    const bool mine = lane < n;
+    const SoaT<float> st = SoaT<float>::make(b.state, B, CP_STATE_FIELDS);
+    const uint32_t o = SoaT<float>::eoff(mine ? row : ch.lo);
+    auto ldint = [&](int f) { return (int32_t)__float_as_uint(st.ld(f, o)); };
+    const bool live = mine && ldint(CP_SF_DONE) == 0;
+    if (mine && !live) policy_zero_action<KIND>(pol.actions_out, (size_t)row);
+    if (__builtin_amdgcn_ballot_w64(live) == 0) return;  // every env of the chunk is done
+
+    int amax = 0;
+    for (int l = 0; l <= pol.num_layers; ++l) amax = pol.width[l] > amax ? pol.width[l] : amax;
+    const int ES = cps::policy_env_stride(pol.group, B), tile = amax * ES;
+    float* const wl = lds + 2 * tile;
+    {   // the chunk's obs rows (contiguous in obs_in) into tile 0, transposed to [unit][env]
+        const int nin = pol.width[0], total = n * nin;
+        const float* obs = pol.obs_in + (size_t)ch.lo * nin;
+        for (int f = lane; f < total; f += WAVE) {
+            const int e = f / nin;
+            lds[(f - e * nin) * ES + e] = obs[f];
+        }
+    }
+    const float* wsrc = pol.weights + (uint64_t)ch.member * (uint64_t)pol.floats;  // 64-bit: passes 4 GiB
+    int half = 0;
+    for (int l = 0; l < pol.num_layers; ++l) {
+        const int nin = pol.width[l], nout = pol.width[l + 1], stride = nin | 1;
+        const bool hidden = l + 1 < pol.num_layers;
+        member_stage_weights(wsrc, nin, nout, wl, lane);
+        __syncthreads();
+        const float* src = lds + half * tile;
+        float* dst = lds + (half ^ 1) * tile;
+        for (int jb = 0; jb < nout; jb += WAVE) {
+            const bool store = jb + lane < nout;
+            const int j = store ? jb + lane : nout - 1;  // lanes past the last unit repeat it, unstored
+            const int fb = nout * nin + j, jbias = fb / nin;
+            const float bias = wl[jbias * stride + (fb - jbias * nin)];
+            const float* wrow = wl + j * stride;
+            int e0 = 0;
+            for (; e0 + 4 < n; e0 += 16) member_block<16>(wrow, bias, src + e0, dst + j * ES + e0, ES, nin, hidden, store);
+            for (; e0 < n; e0 += 4) member_block<4>(wrow, bias, src + e0, dst + j * ES + e0, ES, nin, hidden, store);
+        }
+        __syncthreads();
+        wsrc += nout * nin + nout;
+        half ^= 1;
+    }
+    if (!live) return;
+    const float* zt = lds + half * tile + lane;  // the last layer's tile: unit j of this lane's env
+    float a[4];
+    policy_head<KIND>(pol, [&](int j) { return zt[j * ES]; }, pol.noise ? pol.noise + (size_t)row * 4 : nullptr, ldint(CP_SF_STEPS), ldint(CP_SF_EPISODE),
+                      (uint64_t)(cfg.env_id_offset + row), pol.actions_out, (size_t)row, a);
 }

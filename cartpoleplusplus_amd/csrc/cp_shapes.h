@@ -1,7 +1,11 @@
 // cp_shapes.h — which CP_SHAPE_* a handle's step and autoreset kernels run on, in plain host C++ (no HIP):
 // the resolver behind cp_create / cp_set_lqr / cp_set_kernel_shape, the checks of cp_set_kernel_shape's
 // requests, and the two facts the launchers (cp_env.h) share with it.  tests/shape_table.cpp pins it on the CPU.
+// Also cp_policy_act's kernel choice for a policy population and the member path's work split, which the kernel
+// (cp_policy.h) and the launcher share; tests/policy_runs.cpp pins those.
 #pragma once
+#include <stddef.h>
+
 #include "../../include/cartpole_amd.h"
 
 namespace cps {
@@ -84,6 +88,76 @@ inline Shapes resolve_shapes(const ShapeInputs& in) {
     if (in.step_req != CP_SHAPE_AUTO) s.step = in.step_req;
     if (in.reset_req != CP_SHAPE_AUTO) s.reset = in.reset_req;
     return s;
+}
+
+// ---- cp_policy_act's kernel for a policy population (cp_policy.h)
+#ifdef __HIPCC__
+#define CPS_HD __host__ __device__ inline
+#else
+#define CPS_HD inline
+#endif
+
+enum PolicyPath {
+    POLICY_SHARED,  // population <= 1: the lane-per-env kernel, one weight set
+    POLICY_WAVE,    // every wave of the lane-per-env kernel serves one member (scalar weight loads stay)
+    POLICY_MEMBER,  // a wave's lanes would belong to several members: one member run per wave
+};
+inline PolicyPath policy_path(int population, int group, int64_t env_id_offset) {
+    if (population <= 1) return POLICY_SHARED;
+    return (group % 64 == 0 && env_id_offset % 64 == 0) ? POLICY_WAVE : POLICY_MEMBER;
+}
+
+// The member path's work split.  A member run is a maximal stretch of consecutive local envs with one member:
+// run r holds the global ids [(k0 + r) G, (k0 + r + 1) G) cut to the handle's [off, off + B), k0 = off / G, and
+// is served in chunks of at most 64 envs, one chunk per wave (block): block = r * chunks_per_run + c.  The first
+// and last run can be short, so their trailing chunks can be empty.
+struct PolicyRuns {
+    int64_t k0;          // the first run's global group index
+    int runs;            // member runs that meet [off, off + B)
+    int chunks_per_run;  // ceil(min(G, B) / 64)
+};
+CPS_HD PolicyRuns policy_runs(int64_t off, int group, int B) {
+    PolicyRuns r;
+    r.k0 = off / group;
+    r.runs = (int)((off + B - 1) / group - r.k0) + 1;
+    r.chunks_per_run = ((group < B ? group : B) + 63) / 64;
+    return r;
+}
+struct PolicyChunk {
+    int lo, n;       // local envs [lo, lo + n), n <= 64; n <= 0: an empty chunk
+    int64_t member;  // ((off + lo) / G) % P
+};
+CPS_HD PolicyChunk policy_chunk(int64_t off, int group, int population, int B, const PolicyRuns& r, int block) {
+    const int run = block / r.chunks_per_run, c = block - run * r.chunks_per_run;
+    const int64_t k = r.k0 + run;
+    const int64_t g0 = k * group > off ? k * group : off;                          // the run, in global ids
+    const int64_t g1 = (k + 1) * group < off + B ? (k + 1) * group : off + B;
+    PolicyChunk ch;
+    ch.lo = (int)(g0 - off) + c * 64;
+    const int end = (int)(g1 - off);
+    ch.n = (end - ch.lo < 64 ? end - ch.lo : 64);
+    ch.member = k % population;
+    return ch;
+}
+
+// The member path's LDS (floats), per block: two activation tiles [width][env stride] and one layer's weights
+// with odd row strides (policy_env_stride / policy_weight_floats are what the kernel indexes with).
+CPS_HD int policy_env_stride(int group, int B) {
+    const int n = group < B ? (group < 64 ? group : 64) : (B < 64 ? B : 64);  // the longest chunk
+    const int es = n <= 4 ? 4 : (n + 15) / 16 * 16;  // env blocks of 4, or of 16 (cp_policy.h)
+    return es % 8 == 0 ? es + 4 : es;                // 16-byte rows whose 8-lane store groups cover 32 banks
+}
+CPS_HD int policy_weight_floats(int nin, int nout) {  // W rows at stride nin | 1, then b continuing that grid
+    return (nout + (nout + nin - 1) / nin) * (nin | 1);
+}
+inline size_t policy_member_lds_bytes(const int32_t* width, int num_layers, int group, int B) {
+    int amax = 0, wmax = 0;
+    for (int l = 0; l <= num_layers; ++l) amax = width[l] > amax ? width[l] : amax;
+    for (int l = 0; l < num_layers; ++l) {
+        const int w = policy_weight_floats(width[l], width[l + 1]);
+        wmax = w > wmax ? w : wmax;
+    }
+    return sizeof(float) * ((size_t)2 * amax * policy_env_stride(group, B) + (size_t)((wmax + 3) & ~3));
 }
 
 }  // namespace cps

@@ -6,6 +6,12 @@
 The packed tensor holds the layers one after another, per layer W[out][in] row-major, then b[out].
 The library reads it at every launch and never copies it: keep it alive while the policy is set, and
 write new weights into it in place (`policy.repack`) to have the next launch use them.
+
+A population is P networks of one architecture behind one handle: `group` consecutive global env ids share a
+member, and the members wrap (`member_of`):
+
+    packed, pol = policy.pack_population([actor_0, ..., actor_15], "sample", group=4096)   # packed (16, F)
+    policy.repack(packed[3], actor_3)                          # member 3 alone, in place
 """
 import ctypes as C
 
@@ -71,6 +77,65 @@ def pack(layers, head, epsilon=0.0, seed=0, device="cuda"):
         native.check(None, -1, "cp_policy_floats")
     if n != packed.numel():
         raise native.CartpoleError(f"policy: packed {packed.numel()} floats, cp_policy_floats says {n}")
+    return packed, pol
+
+
+def _is_stacked(members):
+    """One stacked population [(W (P, out, in), b (P, out)), ...] rather than a list of members."""
+    if isinstance(members, torch.nn.Module) or not len(members):
+        return False
+    first = members[0]
+    return (isinstance(first, (tuple, list)) and len(first) == 2 and hasattr(first[0], "ndim") and first[0].ndim == 3)
+
+
+def member_of(gid, group, population):
+    """The member that the env with global id `gid` (env_id_offset + i; an int or an integer array) reads:
+    (gid // group) % population."""
+    return (gid // group) % population
+
+
+def pack_population(members, head, group, epsilon=0.0, seed=0, device="cuda"):
+    """-> (packed (P, F) float32 device tensor, abi.cp_policy pointing at it) for P members of one architecture:
+    a list of nn.Sequentials or of [(W, b), ...] lists, or one already stacked list [(W (P, out, in), b (P, out)),
+    ...].  packed[m] is what pack(members[m]) gives.  Head, epsilon and seed are shared by all members."""
+    if head not in abi.HEADS:
+        raise ValueError(f"policy: head must be one of {sorted(abi.HEADS)}, got {head!r}")
+    if int(group) < 1:
+        raise ValueError(f"policy: group must be >= 1, got {group}")
+    device = torch.device(device)
+    if _is_stacked(members):
+        pairs = [(torch.as_tensor(W), torch.as_tensor(b)) for W, b in members]
+        P = pairs[0][0].shape[0]
+        if any(W.dim() != 3 or b.dim() != 2 or W.shape[0] != P or b.shape[0] != P for W, b in pairs):
+            raise ValueError("policy: a stacked population needs W (P, out, in) and b (P, out) in every layer")
+        widths, _ = _flat([(W[0], b[0]) for W, b in pairs])   # member 0 stands for the architecture checks
+        packed = torch.cat([t.detach().to(device=device, dtype=torch.float32).reshape(P, -1)
+                            for W, b in pairs for t in (W, b)], dim=1).contiguous()
+    else:
+        members = list(members)
+        if not members:
+            raise ValueError("policy: a population needs at least one member")
+        flat = [_flat(m) for m in members]
+        widths = flat[0][0]
+        for k, (w, _) in enumerate(flat):
+            if w != widths:
+                raise ValueError(f"policy: member {k} has widths {w}, member 0 has {widths} (one architecture per population)")
+        packed = torch.stack([torch.cat([p.to(device) for p in parts]) for _, parts in flat]).contiguous()
+    pol = abi.cp_policy()
+    pol.num_layers = len(widths) - 1
+    for k, w in enumerate(widths):
+        pol.width[k] = w
+    pol.head = abi.HEADS[head]
+    pol.epsilon = float(epsilon)
+    pol.seed = int(seed)
+    pol.weights = packed.data_ptr()
+    pol.population = packed.shape[0]
+    pol.group = int(group)
+    n = native.load().cp_policy_floats(C.byref(pol))
+    if n < 0:
+        native.check(None, -1, "cp_policy_floats")
+    if n != packed.shape[1]:
+        raise native.CartpoleError(f"policy: {packed.shape[1]} floats per member, cp_policy_floats says {n}")
     return packed, pol
 
 

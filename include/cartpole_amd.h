@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define CP_ABI_VERSION 7
+#define CP_ABI_VERSION 8
 
 /* Bodies, in the reference's loadURDF order (bullet_cartpole.py:154-160). */
 #define CP_BODY_GROUND 0
@@ -285,7 +285,16 @@ int cp_rollout(cp_handle* h, int steps, const void* actions, int action_kind, fl
  *           u_k = (w_k >> 8) * 2^-24; if u0 < epsilon: a = ((w1 >> 8) * 5) >> 24; else m = max z,
  *           e_j = expf(z_j - m), S = e_0 + .. + e_4 in order, a = the smallest index whose running sum
  *           exceeds u2 * S (4 if none does).
- * An env that is done before a step (no autoreset) is not evaluated; its actions_out entry is 0. */
+ * An env that is done before a step (no autoreset) is not evaluated; its actions_out entry is 0.
+ *
+ * Populations (population = P > 1): weights holds P weight sets [P][F], F = cp_policy_floats(p), each
+ * packed as above, and env i reads member ((env_id_offset + i) / group) % P (64-bit arithmetic): group
+ * consecutive global env ids share a member, and the members wrap (P * group may be smaller than the global
+ * batch).  The member depends on the global id only, so a sharded batch maps envs to members as the
+ * unsharded one does.  Architecture, head, epsilon and seed are shared by all members, and the arithmetic
+ * above is unchanged: only which W, b an env reads differs.  The library picks the kernel (one member per
+ * wave when group and env_id_offset are multiples of 64, one member run per wave otherwise); both give
+ * the same bits. */
 #define CP_POLICY_MAX_LAYERS 4      /* dense layers incl. the output layer (ddpg's 100,100,50 + head) */
 #define CP_POLICY_MAX_WIDTH  128    /* widest layer, input included (14*R <= 128) */
 #define CP_HEAD_TANH   0  /* continuous, out width 4 (a00 a01 a10 a11): the ddpg/naf actor head */
@@ -298,12 +307,15 @@ typedef struct cp_policy {
     int32_t head;
     float   epsilon;                          /* SAMPLE only, in [0,1] */
     uint64_t seed;                            /* SAMPLE only: Philox key */
-    const float* weights;                     /* device, caller-owned, read at every launch */
+    const float* weights;                     /* device, caller-owned, read at every launch; [P][F] for a population */
+    int32_t population;                       /* P: number of weight sets; 0 or 1 = one policy for all envs */
+    int32_t group;                            /* G: consecutive global env ids per member; read only when population > 1 */
 } cp_policy;
 
-/* Number of weight floats of `p`: the sum of out * (in + 1) over its layers.  Applies the checks that need
- * no handle (layer count, widths, head / out width, epsilon); < 0 and cp_last_error(NULL) if invalid.
- * No GPU. */
+/* Number of weight floats of one member of `p`: the sum of out * (in + 1) over its layers (a population's
+ * buffer holds population times as many).  Applies the checks that need no handle (layer count, widths,
+ * head / out width, epsilon, population >= 0, group >= 1 when population > 1); < 0 and cp_last_error(NULL)
+ * if invalid.  No GPU. */
 int64_t cp_policy_floats(const cp_policy* p);
 
 /* Turn the policy on (a copy of *p; the weights stay the caller's) or off (NULL).  Rejected, with the

@@ -10,7 +10,15 @@ JSON line; per-event / per-sample algorithmic bytes as in DESIGN.md §Replay mem
 one warm-up run and the median of --repeats runs each:
     rollout         cp_rollout with precomputed actions (the yardstick)
     act_loop        K x (cp_policy_act + cp_step), "100,50" MLP with the SAMPLE head
-    torch_loop      what a user does without it: K x (torch MLP forward + torch.multinomial + cp_step)"""
+    torch_loop      what a user does without it: K x (torch MLP forward + torch.multinomial + cp_step)
+
+--policy --population [LEGS]: the policy-population legs instead, same net, head and sizes:
+    a  P = 1                      b  P = 1,024, G = 64 (wave-uniform path)     c  P = 16, G = 4,096 (wave-uniform)
+    d  P = B = 65,536, G = 1 (member path)                                      e  P = 2,048, G = 32 (member path)
+cp_policy_act alone over K launches per run for every leg, and the closed loop K x (cp_policy_act + cp_step) for
+a, b and d; d and e also against the weight-streaming floor P * F * 4 bytes / --copy-tbps.  Leg a uses nothing
+newer than set_policy / policy_act, so `--tree OTHER_CHECKOUT --population a` times another build of the library
+with the same code (the P = 1 gate: run the two alternately in one session).  --out writes the JSON to a file."""
 import argparse
 import json
 import os
@@ -18,7 +26,8 @@ import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+_TREE = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.abspath(_TREE))
 from cartpoleplusplus_amd.batched import BatchedCartpole  # noqa: E402
 from cartpoleplusplus_amd.lqr import exact_gains  # noqa: E402
 from cartpoleplusplus_amd.replay_memory import ReplayMemory  # noqa: E402
@@ -78,15 +87,85 @@ def policy_bench(args):
     print(json.dumps(out))
 
 
+POPULATION_LEGS = {"a": (1, None), "b": (1024, 64), "c": (16, 4096), "d": (None, 1), "e": (2048, 32)}   # (P, G); None: B
+
+
+def population_bench(args):
+    import statistics
+    B, K, R = args.batch, args.steps, 3
+    dev = torch.device("cuda", 0)
+    widths = (14 * R, 100, 50, 10)
+    F = sum(o * (i + 1) for i, o in zip(widths[:-1], widths[1:]))
+    env = BatchedCartpole(B, 0, action_repeats=R, initial_force=55.0, autoreset=True, seed=1234)
+    env.reset()
+
+    def run(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    def series(fn):
+        run(fn)  # warm-up
+        ms = [run(fn) for _ in range(args.repeats)]
+        med = statistics.median(ms)
+        return {"ms": ms, "median_ms": med, "spread": (max(ms) - min(ms)) / med}
+
+    out = {"tree": os.path.abspath(_TREE), "batch": B, "steps": K, "repeats": args.repeats,
+           "policy": "42-100-50-10 sample", "floats_per_member": F, "copy_tbps": args.copy_tbps, "legs": {}}
+    for leg in args.population.split(","):
+        P, G = POPULATION_LEGS[leg]
+        P = B if P is None else P
+        g = torch.Generator(device=dev).manual_seed(1234 + P)
+        if P == 1:
+            layers = [(torch.randn((o, i), device=dev, generator=g) / i ** 0.5, torch.randn((o,), device=dev, generator=g) * 0.1)
+                      for i, o in zip(widths[:-1], widths[1:])]
+            env.set_policy(layers, "sample", epsilon=0.05, seed=7)
+        else:
+            stacked = [(torch.randn((P, o, i), device=dev, generator=g) / i ** 0.5,
+                        torch.randn((P, o), device=dev, generator=g) * 0.1) for i, o in zip(widths[:-1], widths[1:])]
+            env.set_policy(stacked, "sample", epsilon=0.05, seed=7, group=G)
+            del stacked
+        res = {"population": P, "group": G, "weight_bytes": P * F * 4}
+        res["act"] = series(lambda: [env.policy_act() for _ in range(K)])
+        res["act_us_per_launch"] = res["act"]["median_ms"] * 1e3 / K
+        if leg in ("a", "b", "d"):
+            env.reset()
+            res["act_step_loop"] = series(lambda: [env.step(env.policy_act()) for _ in range(K)])
+            res["act_step_loop_env_steps_per_s"] = B * K / (res["act_step_loop"]["median_ms"] * 1e-3)
+        if leg in ("d", "e"):   # the member path streams every member's weights once per launch
+            res["floor_us"] = P * F * 4 / (args.copy_tbps * 1e12) * 1e6
+            res["floor_fraction"] = res["floor_us"] / res["act_us_per_launch"]
+        env.set_policy(None)
+        out["legs"][leg] = res
+    if "a" in out["legs"]:
+        for leg, res in out["legs"].items():
+            res["act_over_leg_a"] = res["act_us_per_launch"] / out["legs"]["a"]["act_us_per_launch"]
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--policy", action="store_true")
+    ap.add_argument("--population", nargs="?", const="a,b,c,d,e", default=None, help="with --policy: the population legs")
+    ap.add_argument("--tree", default=None, help="import cartpoleplusplus_amd from this checkout instead of the tool's own")
+    ap.add_argument("--copy-tbps", type=float, default=6.29, help="measured copy bandwidth for the weight-streaming floor")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--ring", type=int, default=1 << 22)
     ap.add_argument("--sample", type=int, default=65536)
     args = ap.parse_args()
+    if args.policy and args.population:
+        return population_bench(args)
     if args.policy:
         return policy_bench(args)
     B, K, R = args.batch, args.steps, 3
