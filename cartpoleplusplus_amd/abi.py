@@ -186,6 +186,24 @@ class cp_policy(C.Structure):
     ]
 
 
+# ---- in-kernel exploration noise of the continuous heads (include/cartpole_amd.h: cp_policy_noise)
+CP_NOISE_OFF, CP_NOISE_GAUSSIAN, CP_NOISE_OU = range(3)
+CP_NOISE_RESET_ON_EPISODE = 0x1
+CP_NOISE_CLIP_SYMMETRIC = 0x2
+NOISE_KINDS = {"off": CP_NOISE_OFF, "gaussian": CP_NOISE_GAUSSIAN, "ou": CP_NOISE_OU}
+
+
+class cp_policy_noise(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("flags", C.c_int32),
+        ("theta", C.c_float),
+        ("sigma", C.c_float),
+        ("max_magnitude", C.c_float),
+        ("seed", C.c_uint64),
+    ]
+
+
 def pixels_shape(B, H, W, C_, R):
     """Raster obs per env (H, W, 3, C, R), bullet_cartpole.py:299-306 (camera before repeat)."""
     return (B, H, W, 3, C_, R)

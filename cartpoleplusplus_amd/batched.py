@@ -326,6 +326,43 @@ class BatchedCartpole:
         native.check(self.h, self.lib.cp_policy_act(self.h, _ptr(o), _ptr(n), _ptr(a), self._stream()), "cp_policy_act")
         return a
 
+    def set_policy_noise(self, kind, theta=0.01, sigma=0.2, max_magnitude=1.5, seed=0, reset_on_episode=False,
+                         symmetric_clip=False):
+        """Exploration noise drawn inside policy_act()'s kernel for the continuous heads (cp_set_policy_noise):
+        kind "gaussian" (sigma * N(0, 1), fresh every step) or "ou" (util.OrnsteinUhlenbeckNoise, one process
+        per env and action component: x += theta * -x; x += sigma * N(0, 1); the defaults are that class's, the ddpg
+        agent runs it with theta=0.01, sigma=0.05); None or "off" turns it off and keeps the processes' state.  The draws come from
+        Philox keyed by `seed` on the env's own counters and global id, so they do not depend on the sharding.
+        max_magnitude > 0 clips as the reference does, from above only (util.py:155); symmetric_clip=True clips
+        to [-max_magnitude, max_magnitude]; max_magnitude <= 0 does not clip.  reset_on_episode restarts an
+        env's processes at 0 on the first step of each episode.  With noise on, policy_act() takes no `noise`."""
+        if kind is None or kind == "off":
+            native.check(self.h, self.lib.cp_set_policy_noise(self.h, None), "cp_set_policy_noise")
+            return
+        if kind not in abi.NOISE_KINDS:
+            raise ValueError(f"policy noise: kind must be one of {sorted(abi.NOISE_KINDS)} or None, got {kind!r}")
+        p = abi.cp_policy_noise()
+        p.kind = abi.NOISE_KINDS[kind]
+        p.flags = (abi.CP_NOISE_RESET_ON_EPISODE if reset_on_episode else 0) | \
+                  (abi.CP_NOISE_CLIP_SYMMETRIC if symmetric_clip else 0)
+        p.theta, p.sigma, p.max_magnitude = float(theta), float(sigma), float(max_magnitude)
+        p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        native.check(self.h, self.lib.cp_set_policy_noise(self.h, C.byref(p)), "cp_set_policy_noise")
+
+    @property
+    def policy_noise(self):
+        """(B, 2, 2) float32: the noise last added per env by policy_act() (the OU state x, or the last Gaussian
+        draw; cp_policy_noise_get).  Assigning a (B, 2, 2) float32 tensor sets it, None zeroes it."""
+        x = torch.empty((self.B, 2, 2), device=self.device, dtype=torch.float32)
+        native.check(self.h, self.lib.cp_policy_noise_get(self.h, _ptr(x), self._stream()), "cp_policy_noise_get")
+        return x
+
+    @policy_noise.setter
+    def policy_noise(self, x):
+        if x is not None:
+            x = _device_buffer(x, (self.B, 2, 2), torch.float32, self.device, "policy noise")
+        native.check(self.h, self.lib.cp_policy_noise_set(self.h, _ptr(x), self._stream()), "cp_policy_noise_set")
+
     def set_bump_forces(self, forces):
         """Parity mode (bump_mode='host'): LINK-frame bump forces (B, 30, 2, 2).  float64 input goes
         through cp_set_bump_forces64 (an fp64 handle keeps the reference's doubles, an fp32 handle

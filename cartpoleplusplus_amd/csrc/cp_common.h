@@ -146,6 +146,13 @@ struct Pol {
     int32_t population;    // P weight sets [P][floats]; <= 1: one policy for all envs
     int32_t group;         // G consecutive global env ids per member (population > 1)
     int64_t floats;        // F: one member's weight floats
+    // in-kernel exploration noise (cp_set_policy_noise; appended likewise): the caller's cp_policy_noise fields
+    // and the handle's state rows
+    int32_t noise_kind;    // CP_NOISE_*; OFF: the caller's noise pointer (or none) is the head's n
+    int32_t noise_flags;
+    float noise_theta, noise_sigma, noise_max;
+    uint64_t noise_seed;
+    float* noise_state;    // [B][4]: the OU state x, or the last Gaussian draw
 };
 
 // Per-handle device buffers.  `state` and `scratch` hold the handle's real type.

@@ -466,6 +466,7 @@ void cp_destroy(cp_handle* h) {
     (void)hipFree(h->count2);
     (void)hipFree(h->b.scratch);
     (void)hipFree(h->pol.scratch);
+    (void)hipFree(h->pol.noise_state);
     (void)hipFree(h->b.stamps);
     (void)hipFree(h->b.stepped);
     (void)hipFree(h->b.pman);
@@ -773,6 +774,14 @@ static int policy_kind(const cp_handle* h) {
 int cp_policy_act(cp_handle* h, const float* obs, const float* noise, void* actions_out, void* stream) {
     if (!h || !obs || !actions_out) return fail(h, "cp_policy_act: null argument");
     if (!h->pol_on) return fail(h, "cp_policy_act: no policy set (cp_set_policy)");
+    if (h->pol.noise_kind != CP_NOISE_OFF) {
+        if (policy_kind(h) != CP_ACTION_CONTINUOUS)
+            return fail(h, "cp_policy_act: in-kernel noise (cp_set_policy_noise) is for the continuous heads (TANH, CLIP); "
+                           "the policy has a discrete head");
+        if (noise)
+            return fail(h, "cp_policy_act: a caller noise pointer together with in-kernel noise (cp_set_policy_noise); "
+                           "pass NULL or turn one of them off");
+    }
     hipStream_t st = (hipStream_t)stream;
     CP_TRY(h, hipSetDevice(h->device));
     cpc::Pol pol = h->pol;
@@ -781,6 +790,70 @@ int cp_policy_act(cp_handle* h, const float* obs, const float* noise, void* acti
     pol.actions_out = actions_out;
     CP_TRY(h, cp::launch_policy_act(policy_kind(h), h->cfg, h->b, pol, st));
     CP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// the checks of a cp_policy_noise that need no handle
+static int policy_noise_check(cp_handle* h, const cp_policy_noise* p, const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (!p) return fail(h, w + "null cp_policy_noise");
+    if (p->kind != CP_NOISE_OFF && p->kind != CP_NOISE_GAUSSIAN && p->kind != CP_NOISE_OU)
+        return fail(h, w + "kind must be CP_NOISE_OFF, _GAUSSIAN or _OU");
+    if (p->flags & ~(CP_NOISE_RESET_ON_EPISODE | CP_NOISE_CLIP_SYMMETRIC))
+        return fail(h, w + "flags holds an unknown CP_NOISE_* bit");
+    if (!std::isfinite(p->sigma) || p->sigma < 0.0f) return fail(h, w + "sigma must be finite and >= 0");
+    if (!std::isfinite(p->theta) || p->theta < 0.0f) return fail(h, w + "theta must be finite and >= 0");
+    return 0;
+}
+
+int cp_policy_noise_check(const cp_policy_noise* p) { return policy_noise_check(nullptr, p, "cp_policy_noise_check"); }
+
+int cp_set_policy_noise(cp_handle* h, const cp_policy_noise* p) {
+    if (!h) return fail(h, "cp_set_policy_noise: null handle");
+    if (!p || p->kind == CP_NOISE_OFF) {
+        h->pol.noise_kind = CP_NOISE_OFF;  // the state rows stay
+        return 0;
+    }
+    if (policy_noise_check(h, p, "cp_set_policy_noise")) return -1;
+    if (h->f64) return fail(h, "cp_set_policy_noise: the MLP policy is fp32 only (not for CP_PRECISION_F64 handles)");
+    if (!h->pol.noise_state) {
+        const size_t bytes = (size_t)h->cfg.num_envs * 4 * sizeof(float);
+        CP_TRY(h, hipSetDevice(h->device));
+        float* s = nullptr;
+        CP_TRY(h, hipMalloc((void**)&s, bytes));
+        hipError_t e = hipMemset(s, 0, bytes);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            (void)hipFree(s);
+            return check(h, e, "cp_set_policy_noise: zeroing the state");
+        }
+        h->pol.noise_state = s;
+    }
+    h->pol.noise_kind = p->kind;
+    h->pol.noise_flags = p->flags;
+    h->pol.noise_theta = p->theta;
+    h->pol.noise_sigma = p->sigma;
+    h->pol.noise_max = p->max_magnitude;
+    h->pol.noise_seed = p->seed;
+    return 0;
+}
+
+int cp_policy_noise_get(cp_handle* h, float* out, void* stream) {
+    if (!h || !out) return fail(h, "cp_policy_noise_get: null argument");
+    if (!h->pol.noise_state) return fail(h, "cp_policy_noise_get: no noise has been set (cp_set_policy_noise)");
+    CP_TRY(h, hipSetDevice(h->device));
+    CP_TRY(h, hipMemcpyAsync(out, h->pol.noise_state, (size_t)h->cfg.num_envs * 4 * sizeof(float), hipMemcpyDeviceToDevice,
+                             (hipStream_t)stream));
+    return 0;
+}
+
+int cp_policy_noise_set(cp_handle* h, const float* in, void* stream) {
+    if (!h) return fail(h, "cp_policy_noise_set: null handle");
+    if (!h->pol.noise_state) return fail(h, "cp_policy_noise_set: no noise has been set (cp_set_policy_noise)");
+    CP_TRY(h, hipSetDevice(h->device));
+    const size_t bytes = (size_t)h->cfg.num_envs * 4 * sizeof(float);
+    if (in) CP_TRY(h, hipMemcpyAsync(h->pol.noise_state, in, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    else CP_TRY(h, hipMemsetAsync(h->pol.noise_state, 0, bytes, (hipStream_t)stream));
     return 0;
 }
 

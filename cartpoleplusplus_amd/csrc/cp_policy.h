@@ -37,6 +37,55 @@ CP_DEV void philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t
     w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
 }
 
+// In-kernel exploration noise of the continuous heads (cp_set_policy_noise; the arithmetic is spelled out in
+// include/cartpole_amd.h and is part of the contract): one Philox block per evaluated env and step gives four
+// Box-Muller normals g; GAUSSIAN x = sigma * g, OU x += theta * (-x), x += sigma * g on the env's state row
+// (util.OrnsteinUhlenbeckNoise, one process per env and action component), then the clip.  The row [4] of
+// noise_state is one 16-byte load (OU only) and one 16-byte store per lane, consecutive lanes on consecutive
+// rows.  -ffp-contract=off: every product and sum below rounds on its own.
+CP_DEV void policy_noise(const cpc::Pol& p, int steps, int episode, uint64_t gid, size_t row, float x[4]) {
+    uint32_t w[4];
+    philox4(0x80000000u + (uint32_t)steps, (uint32_t)episode, (uint32_t)gid, (uint32_t)(gid >> 32),
+            (uint32_t)p.noise_seed, (uint32_t)(p.noise_seed >> 32), w);
+    float g[4];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const float u1 = (float)((w[2 * q] >> 8) + 1u) * 5.9604644775390625e-08f;  // (0, 1]
+        const float u2 = (float)(w[2 * q + 1] >> 8) * 5.9604644775390625e-08f;     // [0, 1)
+        const float r = sqrtf(-2.0f * logf(u1));
+        const float t = 6.283185307179586f * u2;
+        g[2 * q] = r * cosf(t);
+        g[2 * q + 1] = r * sinf(t);
+    }
+    float4* const srow = reinterpret_cast<float4*>(p.noise_state) + row;
+    if (p.noise_kind == CP_NOISE_OU) {
+        const float4 s = *srow;
+        x[0] = s.x; x[1] = s.y; x[2] = s.z; x[3] = s.w;
+        const bool fresh = (p.noise_flags & CP_NOISE_RESET_ON_EPISODE) && steps == 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (fresh) x[c] = 0.0f;
+            const float pull = p.noise_theta * (-x[c]);
+            x[c] = x[c] + pull;
+            const float push = p.noise_sigma * g[c];
+            x[c] = x[c] + push;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) x[c] = p.noise_sigma * g[c];
+    }
+    if (p.noise_max > 0.0f) {
+        const float m = p.noise_max;
+        const bool sym = (p.noise_flags & CP_NOISE_CLIP_SYMMETRIC) != 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (sym && x[c] < -m) x[c] = -m;
+            if (x[c] > m) x[c] = m;  // the default bounds from above only (util.py:155's argument order)
+        }
+    }
+    *srow = make_float4(x[0], x[1], x[2], x[3]);
+}
+
 // The layers of the MLP over the lane's scratch column (coff = env * 4 bytes), with the wave's weights woff
 // floats into p.weights (wave-uniform: 0, or the wave's member of a population): the input x[0 .. width[0]) is
 // in half 0; returns the half that holds the last layer's (linear) outputs.
@@ -95,18 +144,26 @@ CP_DEV int policy_layers(const cpc::Pol& p, uint64_t woff, const SoaF& scr, uint
 }
 
 // The head on one env's last-layer outputs zv(0 .. 3) (continuous) or zv(0 .. 9) (discrete; zv reads the z vector
-// where the kernel keeps it: the scratch column or the LDS tile), the caller's noise row (4 floats or null) and
-// the env's counters before the step: writes actions_out[row] (float4 or char2) and returns the unit action
-// a00 a01 a10 a11 the step scales by action_force.  Shared by both kernels.
+// where the kernel keeps it: the scratch column or the LDS tile), the caller's noise row (4 floats or null; with
+// in-kernel noise on, policy_noise's draw on the env's state row instead) and the env's counters before the step:
+// writes actions_out[row] (float4 or char2) and returns the unit action a00 a01 a10 a11 the step scales by
+// action_force.  Shared by both kernels.
 template <int KIND, typename Z>
 CP_DEV void policy_head(const cpc::Pol& p, const Z& zv, const float* noise, int steps, int episode, uint64_t gid,
                         void* actions_out, size_t row, float a[4]) {
     if constexpr (KIND == CP_ACTION_CONTINUOUS) {
+        float n[4];
+        if (p.noise_kind != CP_NOISE_OFF) {
+            policy_noise(p, steps, episode, gid, row, n);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) n[c] = noise ? noise[c] : 0.0f;
+        }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float z = zv(c);
             if (p.head == CP_HEAD_TANH) z = tanhf(z);
-            a[c] = fminf(fmaxf(z + (noise ? noise[c] : 0.0f), -1.0f), 1.0f);
+            a[c] = fminf(fmaxf(z + n[c], -1.0f), 1.0f);
         }
         reinterpret_cast<float4*>(actions_out)[row] = make_float4(a[0], a[1], a[2], a[3]);
     } else {

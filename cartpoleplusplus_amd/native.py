@@ -24,6 +24,7 @@ EXPORTS = (
     "cp_state_bytes", "cp_set_kernel_shape", "cp_get_kernel_shape", "cp_rollout",
     "cp_nonfinite_counts", "cp_render_kernel_name",
     "cp_policy_floats", "cp_set_policy", "cp_policy_act",
+    "cp_policy_noise_check", "cp_set_policy_noise", "cp_policy_noise_get", "cp_policy_noise_set",
 )
 
 _lib = None
@@ -86,6 +87,10 @@ def load():
         "cp_policy_floats": (C.c_int64, [P(abi.cp_policy)]),
         "cp_set_policy": (I, [VP, P(abi.cp_policy)]),
         "cp_policy_act": (I, [VP, VP, VP, VP, VP]),
+        "cp_policy_noise_check": (I, [P(abi.cp_policy_noise)]),
+        "cp_set_policy_noise": (I, [VP, P(abi.cp_policy_noise)]),
+        "cp_policy_noise_get": (I, [VP, VP, VP]),
+        "cp_policy_noise_set": (I, [VP, VP, VP]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -328,8 +328,65 @@ int cp_set_policy(cp_handle* h, const cp_policy* p);
 
 /* The policy's actions for every env from obs [B][R][2][7] (the obs the caller last received), noise
  * ([B][2][2], may be NULL; continuous heads) and the state's counters: actions_out [B][2][2] f32
- * (TANH, CLIP) or [B][2] i8 (ARGMAX, SAMPLE), which the caller then passes to cp_step. */
+ * (TANH, CLIP) or [B][2] i8 (ARGMAX, SAMPLE), which the caller then passes to cp_step.  With in-kernel noise
+ * on (cp_set_policy_noise, below) the kernel draws n itself: noise must then be NULL and the head continuous. */
 int cp_policy_act(cp_handle* h, const float* obs, const float* noise, void* actions_out, void* stream);
+
+/* ---- In-kernel exploration noise for the continuous heads (ddpg_cartpole.py:86-88, util.py:134-156) ----
+ * With a noise kind set, cp_policy_act's kernels draw the head's n themselves, per evaluated env, instead of
+ * reading the caller's noise pointer.  The draws depend on the env's own counters and global id only, so they
+ * are the same however a batch is sharded (env_id_offset) and whichever population member an env reads.
+ * ABI 8, additive: no existing struct or signature changes.
+ *
+ * Arithmetic (all fp32, every product and sum rounded on its own; part of the contract).  For an env that is
+ * evaluated (not done), steps / episode its counters before the step, gid = env_id_offset + i:
+ *   1. (w0..w3) = Philox4x32-10(ctr = (0x80000000 + steps, episode, gid_lo, gid_hi), key = the noise seed).
+ *      (The SAMPLE head's first counter word is 0x40000000 + 2*steps + c and its key is cp_policy.seed.)
+ *   2. for q = 0, 1:  u1 = (float)((w[2q] >> 8) + 1) * 2^-24      (in (0, 1])
+ *                     u2 = (float)(w[2q+1] >> 8) * 2^-24          (in [0, 1))
+ *                     r = sqrtf(-2.0f * logf(u1));  t = 6.283185307179586f * u2
+ *                     g[2q] = r * cosf(t);  g[2q+1] = r * sinf(t)
+ *   3. component c of g goes to a00 a01 a10 a11 (c = 0..3); x is the env's state row [4].
+ *   4. GAUSSIAN:  x = sigma * g[c]
+ *   5. OU:        if RESET_ON_EPISODE is set and steps == 0: x = 0
+ *                 x = x + theta * (-x)     (the product rounded, then the sum)
+ *                 x = x + sigma * g[c]     (likewise)
+ *   6. clip, skipped when max_magnitude <= 0: by default x = min(x, max_magnitude), which is what
+ *      util.py:155 computes (np.clip(max, -max, state): its argument order bounds the state from above
+ *      only; reproduced as cp_set_readback's reference_bug reproduces :224); CLIP_SYMMETRIC gives
+ *      x = min(max(x, -max_magnitude), max_magnitude).
+ *   7. x is stored to the state row and is the head's n: a = min(max(z_or_tanhf(z) + x, -1), 1).
+ * An env that is done is not evaluated: no draw is made for it and its state row is untouched.
+ *
+ * Storage: the handle owns a [B][4] float buffer, allocated and zeroed by the first cp_set_policy_noise that
+ * turns noise on and freed by cp_destroy.  In OU mode it is the process state x, in GAUSSIAN mode the last
+ * draw.  Turning noise off keeps it, so a later OU run continues the same processes. */
+#define CP_NOISE_OFF      0
+#define CP_NOISE_GAUSSIAN 1   /* n = sigma * g, fresh every step */
+#define CP_NOISE_OU       2   /* util.OrnsteinUhlenbeckNoise, one process per env and action component */
+#define CP_NOISE_RESET_ON_EPISODE 0x1  /* x = 0 before the update when the env's step counter is 0 */
+#define CP_NOISE_CLIP_SYMMETRIC   0x2  /* clip to [-max, +max]; default: the reference's behaviour, see above */
+typedef struct cp_policy_noise {
+    int32_t kind, flags;
+    float theta, sigma, max_magnitude;   /* max_magnitude <= 0: no clip */
+    uint64_t seed;                       /* Philox key, independent of cp_policy.seed */
+} cp_policy_noise;
+
+/* The checks that need no handle: an unknown kind, unknown flag bits, sigma or theta that is not finite or is
+ * below 0.  0 if valid; < 0 and the cause in cp_last_error(NULL) otherwise.  No GPU. */
+int cp_policy_noise_check(const cp_policy_noise* p);
+
+/* Turn in-kernel noise on (a copy of *p) or off (NULL, or kind CP_NOISE_OFF; the state buffer is kept).
+ * Rejected: fp64 handles and whatever cp_policy_noise_check rejects.  Independent of cp_set_policy: either may
+ * be called first.  With noise on, cp_policy_act rejects a policy with a discrete head (ARGMAX, SAMPLE), and a
+ * non-NULL caller noise pointer.  cp_step and cp_rollout are unaffected. */
+int cp_set_policy_noise(cp_handle* h, const cp_policy_noise* p);
+
+/* Stream-ordered copies of the state buffer [B][2][2] (the noise last added per env: x in OU mode, the last
+ * draw in GAUSSIAN mode) to and from device memory; in = NULL zeroes it.  Rejected before any
+ * cp_set_policy_noise has turned noise on (there is no buffer yet). */
+int cp_policy_noise_get(cp_handle* h, float* out, void* stream);
+int cp_policy_noise_set(cp_handle* h, const float* in, void* stream);
 
 /* Optional per-substep 12-state readback of both poles (bullet_cartpole.py:212-234,
  * exposed there as monkey_positions / monkey_velocities):

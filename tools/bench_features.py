@@ -18,7 +18,14 @@ one warm-up run and the median of --repeats runs each:
 cp_policy_act alone over K launches per run for every leg, and the closed loop K x (cp_policy_act + cp_step) for
 a, b and d; d and e also against the weight-streaming floor P * F * 4 bytes / --copy-tbps.  Leg a uses nothing
 newer than set_policy / policy_act, so `--tree OTHER_CHECKOUT --population a` times another build of the library
-with the same code (the P = 1 gate: run the two alternately in one session).  --out writes the JSON to a file."""
+with the same code (the P = 1 gate: run the two alternately in one session).  --out writes the JSON to a file.
+
+--policy --noise [LEGS]: the exploration-noise legs (DESIGN.md §9.5 "Exploration noise"): ddpg's actor
+("100,100,50", TANH head) with OU noise at the agent's defaults, at B = 4,096 with R = 2 (C2) and at B = 65,536:
+    off     cp_policy_act alone, noise off (nothing newer than set_policy / policy_act, so `--tree OTHER_CHECKOUT
+            --noise off` times the parent build: the noise-off gate, the two builds alternating in one session)
+    kernel  K x (policy_act with in-kernel OU + step)
+    torch   K x (the caller's torch OU update of INTEGRATION.md + policy_act(noise=x) + step)"""
 import argparse
 import json
 import os
@@ -151,9 +158,84 @@ def population_bench(args):
             f.write(line + "\n")
 
 
+NOISE_SIZES = ((4096, 2), (65536, 3))   # (B, R): C2, and the full-size batch of the other policy legs
+
+
+def noise_bench(args):
+    """ddpg's actor ("100,100,50", TANH head, continuous actions) with OU exploration noise at the agent's
+    defaults (theta = 0.01, sigma = 0.05), per size one handle, K = --steps per run, one warm-up run and the
+    median of --repeats runs per leg."""
+    import statistics
+    K = args.steps
+    dev = torch.device("cuda", 0)
+    theta, sigma = 0.01, 0.05
+
+    def run(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    def series(fn):
+        run(fn)  # warm-up
+        ms = [run(fn) for _ in range(args.repeats)]
+        med = statistics.median(ms)
+        return {"ms": ms, "median_ms": med, "spread": (max(ms) - min(ms)) / med}
+
+    out = {"tree": os.path.abspath(_TREE), "steps": K, "repeats": args.repeats, "policy": "14R-100-100-50-4 tanh",
+           "ou": {"theta": theta, "sigma": sigma}, "sizes": {}}
+    for B, R in NOISE_SIZES:
+        g = torch.Generator(device=dev).manual_seed(1234 + B)
+        widths = (14 * R, 100, 100, 50, 4)
+        layers = [(torch.randn((o, i), device=dev, generator=g) / i ** 0.5, torch.randn((o,), device=dev, generator=g) * 0.1)
+                  for i, o in zip(widths[:-1], widths[1:])]
+        env = BatchedCartpole(B, 0, action_repeats=R, initial_force=55.0, autoreset=True, seed=1234)
+        env.set_policy(layers, "tanh")
+        env.reset()
+        res = {"action_repeats": R}
+        for leg in args.noise.split(","):
+            if leg == "off":        # cp_policy_act alone, no noise: nothing newer than set_policy / policy_act
+                res["off_act"] = series(lambda: [env.policy_act() for _ in range(K)])
+                res["off_act_us_per_launch"] = res["off_act"]["median_ms"] * 1e3 / K
+            elif leg == "kernel":   # K x (policy_act with in-kernel OU + step)
+                env.reset()
+                env.set_policy_noise("ou", theta=theta, sigma=sigma, seed=7)
+                res["kernel_act"] = series(lambda: [env.policy_act() for _ in range(K)])
+                res["kernel_act_us_per_launch"] = res["kernel_act"]["median_ms"] * 1e3 / K
+                res["kernel_loop"] = series(lambda: [env.step(env.policy_act()) for _ in range(K)])
+                res["kernel_loop_env_steps_per_s"] = B * K / (res["kernel_loop"]["median_ms"] * 1e-3)
+                env.set_policy_noise(None)
+            elif leg == "torch":    # K x (the caller's torch OU update + policy_act(noise=x) + step)
+                env.reset()
+                x = [torch.zeros((B, 2, 2), device=dev)]
+
+                def torch_loop():
+                    for _ in range(K):
+                        x[0] = x[0] + theta * (0.0 - x[0]) + sigma * torch.randn_like(x[0])
+                        env.step(env.policy_act(noise=x[0]))
+                res["torch_loop"] = series(torch_loop)
+                res["torch_loop_env_steps_per_s"] = B * K / (res["torch_loop"]["median_ms"] * 1e-3)
+            else:
+                raise SystemExit(f"--noise: legs are off, kernel, torch; got {leg!r}")
+        if "kernel_loop" in res and "torch_loop" in res:
+            res["kernel_over_torch"] = res["kernel_loop_env_steps_per_s"] / res["torch_loop_env_steps_per_s"]
+        out["sizes"][str(B)] = res
+        env.close()
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--policy", action="store_true")
+    ap.add_argument("--noise", nargs="?", const="off,kernel,torch", default=None,
+                    help="with --policy: the exploration-noise legs (off, kernel, torch)")
     ap.add_argument("--population", nargs="?", const="a,b,c,d,e", default=None, help="with --policy: the population legs")
     ap.add_argument("--tree", default=None, help="import cartpoleplusplus_amd from this checkout instead of the tool's own")
     ap.add_argument("--copy-tbps", type=float, default=6.29, help="measured copy bandwidth for the weight-streaming floor")
@@ -166,6 +248,8 @@ def main():
     args = ap.parse_args()
     if args.policy and args.population:
         return population_bench(args)
+    if args.policy and args.noise:
+        return noise_bench(args)
     if args.policy:
         return policy_bench(args)
     B, K, R = args.batch, args.steps, 3
