@@ -1794,6 +1794,7 @@ int orc_envs_step_omp(orc_envs* e, const void* actions, int kind, float* obs_out
 }
 void orc_envs_sweeps(const orc_envs* e, int32_t* out) { memcpy(out, e->sweeps, (size_t)e->B * 2 * sizeof(int32_t)); }
 void orc_envs_nonfinite(const orc_envs* e, int32_t* out) { memcpy(out, e->nonfinite, (size_t)e->B * sizeof(int32_t)); }
+void orc_envs_overflow(const orc_envs* e, int32_t* out) { memcpy(out, e->overflow, (size_t)e->B * sizeof(int32_t)); }
 void orc_envs_merged(const orc_envs* e, int32_t* out) { memcpy(out, e->merged, (size_t)e->B * sizeof(int32_t)); }
 void orc_envs_episode_returns(const orc_envs* e, float* ret, int32_t* len) {
     if (ret) memcpy(ret, e->last_ret, (size_t)e->B * sizeof(float));

@@ -90,6 +90,7 @@ def load(precision="f32"):
         "orc_envs_sweeps": (None, [VP, VP]),
         "orc_envs_merged": (None, [VP, VP]),
         "orc_envs_nonfinite": (None, [VP, VP]),
+        "orc_envs_overflow": (None, [VP, VP]),
         "orc_render_frame": (None, [VP, VP, VP, C.c_int, VP]),
         "orc_philox4x32_10": (None, [P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]),
         "orc_sincos_turns": (None, [C.c_float, P(C.c_float), P(C.c_float)]),
@@ -292,6 +293,13 @@ class Envs:
         """(B,) steps / resets that ended with a non-finite body state (cp_nonfinite_counts)."""
         out = np.zeros(self.B, np.int32)
         self.lib.orc_envs_nonfinite(self.h, _ptr(out))
+        return out
+
+    def overflow(self):
+        """(B,) contact rows dropped by the island caps since creation: normal rows past CP_ISLAND_POINTS
+        and friction rows past CP_ISLAND_FRICTION (cp_overflow_counts)."""
+        out = np.zeros(self.B, np.int32)
+        self.lib.orc_envs_overflow(self.h, _ptr(out))
         return out
 
     def sweeps(self):

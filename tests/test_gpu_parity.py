@@ -31,13 +31,20 @@ SHAPE_IDS = ["tp-tp", "lat-lat", "tp-lat", "lat-tp", "wide-wide", "tp-wide", "wi
 shapes = pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
 
 
-def _pair(O, shape=None, **kw):
+def _pair(O, shape=None, mutate=None, precision="f32", oracle=True, **kw):
+    """A GPU handle and an oracle Envs on one config: the defaults, the overrides **kw, then mutate(cfg) (a
+    scene variant of tests/scene_variants.py).  oracle=False: the handle alone (the oracle's side of the run
+    is a recorded one, shared between cases)."""
     cfg = native.default_config(**kw)
+    if mutate is not None:
+        mutate(cfg)
+    if precision == "f64":
+        cfg.precision = abi.CP_PRECISION_F64
     gpu = BatchedCartpole(cfg.num_envs, 0, config=abi.cp_config.from_buffer_copy(cfg))
     if shape is not None:
         gpu.set_kernel_shape(*shape)
         assert gpu.kernel_shape() == tuple(shape)
-    orc = O.Envs(abi.cp_config.from_buffer_copy(cfg))
+    orc = O.Envs(abi.cp_config.from_buffer_copy(cfg), precision=precision) if oracle else None
     return gpu, orc
 
 
@@ -239,6 +246,7 @@ def test_cross_island_contact_merged_solve(oracle_mod, shape):
         _assert_same(_np(go), oo, f"obs step {t}")
         _assert_same(_np(gd), od, f"done step {t}")
     _compare_state(gpu, orc, "after the merged rollout")
+    _assert_same(_np(gpu.overflow_counts()), orc.overflow(), "overflow after the merged rollout")
     assert (merged > 0).sum() >= B * 3 // 4, f"only {(merged > 0).sum()} envs ran a merged solve"
     assert merged.sum() >= 30 * B
 
@@ -430,6 +438,9 @@ def test_cart_friction_config(oracle_mod, shape):
     orc = oracle_mod.Envs(abi.cp_config.from_buffer_copy(cfg))
     _assert_same(_np(gpu.reset()), orc.reset(), "reset")
     _compare_state(gpu, orc, "reset")
+    # ground-cart and cart-pole ask for 8 friction rows of the island's 5: the reset already drops rows
+    assert orc.overflow().all()
+    _assert_same(_np(gpu.overflow_counts()), orc.overflow(), "overflow after the reset")
     rng = np.random.default_rng(2)
     for t in range(70):
         a = rng.integers(0, 5, (B, 2)).astype(np.int8)
@@ -438,6 +449,7 @@ def test_cart_friction_config(oracle_mod, shape):
         _assert_same(_np(go), oo, f"obs step {t}")
         _assert_same(_np(gd), od, f"done step {t}")
     _compare_state(gpu, orc, "after 70 steps")
+    _assert_same(_np(gpu.overflow_counts()), orc.overflow(), "overflow after 70 steps")
 
 
 def test_auto_shapes_by_batch_size():

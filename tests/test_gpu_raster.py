@@ -3,13 +3,20 @@ oracle's ray caster on the same poses, bit for bit, through the C-ABI.
 
 The poses come from the GPU env itself (get_state after the call: the last repeat's
 frame; after a reset every repeat slot holds the reset frame).  The conversion to
-float16 is the reference's (bullet_cartpole.py:289-294), restated in oracle.u8_to_f16."""
+float16 is the reference's (bullet_cartpole.py:289-294), restated in oracle.u8_to_f16.
+
+test_poses_off_the_reference_view leaves the reference view: poses set through cp_set_state
+(tests/raster_poses.py: bodies behind the eye, across the eye plane, around the eye, partly off
+screen), other cameras, colours and box sizes, every frame of every repeat."""
 import numpy as np
 import pytest
 import torch
 
 from cartpoleplusplus_amd import abi, native
 from cartpoleplusplus_amd.batched import BatchedCartpole
+from tests import raster_poses as RP
+from tests import scene_variants as SV
+from tests.test_gpu_parity import _assert_same
 
 pytestmark = pytest.mark.gpu
 
@@ -173,6 +180,48 @@ def test_render_v2_equals_v1_every_pixel(monkeypatch, R, C, W, H):
         out.append(torch.stack(frames).view(torch.int16))
         env.close()
     assert torch.equal(out[0], out[1])
+
+
+@pytest.mark.parametrize("W,H,C,R,v1,kernel", RP.KERNELS, ids=RP.KERNEL_IDS)
+@pytest.mark.parametrize("scene", RP.SCENES)
+def test_poses_off_the_reference_view(oracle_mod, monkeypatch, scene, W, H, C, R, v1, kernel):
+    """Bodies behind the eye, across the eye plane, around the eye, on screen and partly off screen
+    (tests/raster_poses.py: poses set through cp_set_state, then one step), rendered by every small-frame
+    kernel (cp_render_small2_kernel, the round-3 kernel under CP_RENDER_V1=1) and the wave kernel, with the
+    reference cameras, a second camera / light / colour configuration and other box sizes: every frame of
+    every env, camera and repeat bit-exact against the oracle's ray caster.  box_rect's all-behind, behind
+    and clamp branches, the class table and the code seeding see only the reference view elsewhere."""
+    if v1:
+        monkeypatch.setenv("CP_RENDER_V1", "1")
+    else:
+        monkeypatch.delenv("CP_RENDER_V1", raising=False)
+    x = RP.expected(oracle_mod, scene, W, H, C, R)
+    cfg = native.default_config(num_envs=RP.B, action_repeats=R, initial_force=55.0, seed=11)
+    if scene in ("cart", "squat"):
+        SV.apply(cfg, scene)
+    assert bytes(cfg) == bytes(x["cfg"]), "the oracle's expectation is of another config"
+    env = BatchedCartpole(RP.B, 0, config=abi.cp_config.from_buffer_copy(cfg))
+    env.enable_raster(True, raster_config=x["rc"])
+    assert env.render_kernel_name() == kernel
+    env.reset()
+    _assert_same(env.get_state().cpu().numpy(), x["reset_state"], "reset state")
+    env.set_state(torch.from_numpy(x["start"]).cuda())
+    env.step(torch.from_numpy(x["action"]).cuda())
+    # the oracle stepped one repeat at a time to have every repeat's poses: its step counter is R, not 1
+    rows = [f for f in range(abi.CP_STATE_FIELDS) if f != abi.CP_SF_STEPS]
+    _assert_same(env.get_state().cpu().numpy()[rows], x["end"][rows], "state after the step")
+    counts = RP.class_counts(x["poses"][-1], x["rc"], cfg.phys)
+    assert (counts >= 8).all(), dict(zip(RP.CLASS_NAMES, counts.tolist()))
+    got = env.pixels.cpu().numpy().view(np.uint16)
+    assert got.shape == x["frames"].shape
+    if not np.array_equal(got, x["frames"]):
+        bad = np.argwhere((got != x["frames"]).any(axis=(1, 2, 3)))   # (env, camera, repeat)
+        e, c, r = (int(v) for v in bad[0])
+        cls = RP.classify(x["poses"][r, e], x["rc"], cfg.phys, c)
+        raise AssertionError(f"{len(bad)} of {RP.B * C * R} frames differ; first env {e} cam {c} repeat {r}: "
+                             f"{int((got[e, ..., c, r] != x['frames'][e, ..., c, r]).sum())} channel values, body "
+                             f"classes {[RP.CLASS_NAMES[k] for k in cls]}")
+    env.close()
 
 
 def test_render_kernel_name_is_the_launchers_choice(monkeypatch):
