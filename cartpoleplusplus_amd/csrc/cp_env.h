@@ -1,13 +1,19 @@
-// cp_env.h — the batched env's kernels over `real` (step, reset, init) and their host
+// cp_env.h — the batched env's kernels over `real` (step, reset, rollout, init) and their host
 // launchers; included once per real type after cp_math.h and cp_physics.h (cp_common.h):
 // namespace cp (fp32, cp_kernels.hip) and cp64 (fp64, cp_kernels64.hip).
 //
-//   cp_step_kernel   R x S substeps fused in one launch; force applied after each
-//                    substep (bullet_cartpole.py:199-207); obs at each repeat end
-//                    (:237 -> :298-311); steps/done/reward (:239-260).  Finishing
-//                    envs are appended to a reset list by wave ballot compaction.
-//   cp_reset_kernel  spawn poses, 100 settle + 30 bump substeps (:313-346), over a
-//                    compacted list of env ids (dense waves, no idle lanes).
+//   cp_step_kernel    R x S substeps fused in one launch; force applied after each
+//                     substep (bullet_cartpole.py:199-207); obs at each repeat end
+//                     (:237 -> :298-311); steps/done/reward (:239-260).  Finishing
+//                     envs are appended to a reset list by wave ballot compaction.
+//   cp_reset_kernel   spawn poses, 100 settle + 30 bump substeps (:313-346), over a
+//                     compacted list of env ids (dense waves, no idle lanes).
+//   cp_rollout_kernel K env-steps of every env in one launch, each finishing episode reset inline.
+//
+// The "episode parts" above the kernels are the rules with one definition for every kernel that needs them:
+// episode_over, begin_reset, action_forces / push_own_cart / lqr_gains, wave_append, opaque_index / lane_island /
+// late_mem.  The step's and the reset's ends and the repeat's obs row are still written out in each kernel: as
+// shared functions they moved SGPR or SGPR-spill counts of some kernels.
 //
 // Memory: per-env state is SoA real [CP_STATE_FIELDS][B] in HBM (coalesced per field);
 // inside a launch the env lives in VGPRs and its contact rows in a per-wave LDS pool
@@ -360,6 +366,57 @@ CP_DEV void wave_append(bool want, int32_t* counter, int32_t* list, int value) {
     if (want) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = value;
 }
 
+// ---- episode parts (with begin_reset, wave_append): shared only where every caller keeps its register counts
+// The env index through an opaque register copy wherever code after (or inside) the substep loop forms an
+// address: the 64-bit per-lane addresses formed at the top otherwise live through the loop, or are hoisted out
+// of it, and are spilled (the step kernel's scratch frame, written at the top and read back at the end).
+CP_DEV int opaque_index(int i) { asm volatile("" : "+v"(i)); return i; }
+// the lane's island (parity) from the lane id, where late offsets need it (a kept copy of it was spilled)
+CP_DEV int lane_island() { return (int)(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 1u); }
+// The lane's SoA offsets where the substeps and the epilogue address the state.  The throughput shape (and fp64)
+// rebuilds them from the opaque index instead of keeping the ones formed at the top live through the loop
+// (scratch 48 -> 24 B/lane); the 0-scratch latency kernels (KEEP) keep G (a lone wave pays the rebuild: latency
+// reset list +2.6 %).  OPAQUE = false: `i` is an opaque copy already.  isl < 0: lane_island().
+template <bool KEEP, bool OPAQUE = true>
+CP_DEV Mem late_mem(const Mem& G, const Bufs& b, int B, int i, int isl = -1) {
+    if constexpr (KEEP) return G;
+    else return Mem::make(b.state, b.scratch, B, OPAQUE ? opaque_index(i) : i, isl < 0 ? lane_island() : isl, b.pman);
+}
+// One env-step's action forces, action_force * action (bullet_cartpole.py:201-207): continuous
+// float4 (a00 a01 a10 a11) or discrete int8 x 2 through kDiscrete (out-of-range index = 0).
+template <int KIND>
+CP_DEV void action_forces(const void* actions, size_t row, real F, real f[4]) {
+    real a00, a01, a10, a11;
+    if constexpr (KIND == CP_ACTION_CONTINUOUS) {
+        const float4 a = reinterpret_cast<const float4*>(actions)[row];
+        a00 = a.x; a01 = a.y; a10 = a.z; a11 = a.w;
+    } else {
+        const char2 a = reinterpret_cast<const char2*>(actions)[row];
+        int k0 = a.x, k1 = a.y;
+        k0 = (k0 < 0 || k0 >= CP_NUM_DISCRETE) ? 0 : k0;
+        k1 = (k1 < 0 || k1 >= CP_NUM_DISCRETE) ? 0 : k1;
+        a00 = kDiscrete[k0][0]; a01 = kDiscrete[k0][1];
+        a10 = kDiscrete[k1][0]; a11 = kDiscrete[k1][1];
+    }
+    f[0] = a00 * F; f[1] = a01 * F; f[2] = a10 * F; f[3] = a11 * F;
+}
+// after a substep: the action force on the own cart, under the LQR policy with the control force u of the
+// pre-step state on top (disturbance + control, random_action_agent.py:897-901)
+template <bool LQR>
+CP_DEV void push_own_cart(Own& O, real fa, real fb, const real u[2]) {
+    if constexpr (LQR) apply_force_link(O, fa + u[0], fb + u[1]);
+    else apply_force_link(O, fa, fb);
+}
+CP_DEV const float* lqr_gains(const Lqr& lq, int i) { return lq.gains + (lq.per_env ? (size_t)i * 32 : 0); }
+// when an episode is over after its step number `steps` (bullet_cartpole.py:239-253, and the LQR agent's
+// thresholds); every lane of the env calls it (bounds_exceeded: DPP)
+CP_DEV bool episode_over(int steps, const Own& O, const cp_config& cfg, bool lqr_done) {
+    bool done = steps >= cfg.max_episode_len;
+    if (cfg.done_on_bounds && bounds_exceeded(O, cfg)) done = true;
+    if (lqr_done) done = true;
+    return done;
+}
+
 // LAT = false: the throughput shape of the step kernel (2 waves per SIMD), for reset bursts
 // (fixed-length episodes end together).  LAT = true: one wave per SIMD with 512 registers and
 // fast-form rows, for the short lists of desynchronised episodes (bounds termination), where
@@ -372,6 +429,7 @@ __attribute__((amdgpu_waves_per_eu(LAT ? 1 : CP_WAVES_PER_EU, LAT ? 1 : CP_WAVES
 cp_reset_kernel(cp_config cfg, Bufs b, float* obs_out) {
     static_assert(!WIDE || (LAT && !PM && !SLP), "WIDE: latency shape, default contact model");
     constexpr int LW = WIDE ? WIDE : 2;  // lanes per env
+    constexpr bool KEEP = LAT && !kF64;  // late_mem
     __shared__ real lds_pool[(PM ? POOL_FLOATS_PM : POOL_FLOATS) * WAVE];
     const int B = cfg.num_envs;
     const int t = blockIdx.x * WAVE + threadIdx.x;
@@ -383,13 +441,6 @@ cp_reset_kernel(cp_config cfg, Bufs b, float* obs_out) {
     const bool lead = (t & (LW - 1)) == 0;
     const bool owner = (t & (LW - 1)) < 2;  // the lane pair that stores the env's state (WIDE: replica 0)
     const int i = b.list[t / LW];
-    // the env index through an opaque copy where the substeps and the epilogue address the state: the
-    // lane's SoA offsets are rebuilt there instead of living through the 130 substeps (cp_step_kernel)
-    auto late_i = [&]() {
-        int x = i;
-        asm volatile("" : "+v"(x));
-        return x;
-    };
     // WIDE: the replicas of an island share its pool column (the replica-0 lane's)
     real* pool0 = lds_pool + (threadIdx.x & ~(LW - 1u));
     real* pool = WIDE ? pool0 + isl : lds_pool + threadIdx.x;
@@ -407,8 +458,8 @@ cp_reset_kernel(cp_config cfg, Bufs b, float* obs_out) {
     int ov = 0;
     const int nsub = cfg.settle_steps + cfg.initial_force_steps;
     for (int s = 0; s < nsub; ++s) {
-        const Mem Gs = (LAT && !kF64) ? G : Mem::make(b.state, b.scratch, B, late_i(), isl, b.pman);
-        substep<LAT && !kF64, true, true, PM, SLP, WIDE>(O, cfg.phys, L, pool, pool0, ov, Gs, ST);
+        const Mem Gs = late_mem<KEEP>(G, b, B, i, isl);
+        substep<KEEP, true, true, PM, SLP, WIDE>(O, cfg.phys, L, pool, pool0, ov, Gs, ST);
         const int k = s - cfg.settle_steps;
         if (k >= 0) {  // bump the lane's own cart (cart, then cart2 in the reference's draw order)
             real fx, fy;
@@ -422,8 +473,8 @@ cp_reset_kernel(cp_config cfg, Bufs b, float* obs_out) {
     CP_RT(r1);
     flush_stamps(ST, b.stamps + 16, k1 - k0, r0, r1);  // the reset kernel's counters: slots 16-26
 #endif
-    const Mem Ge = (LAT && !kF64) ? G : Mem::make(b.state, b.scratch, B, late_i(), isl, b.pman);
-    const int il = late_i();
+    const Mem Ge = late_mem<KEEP>(G, b, B, i, isl);
+    const int il = opaque_index(i);
     if (owner) store_own(O, Ge, isl);  // each lane stores its own island
     if constexpr (SLP) store_sleep(O, Ge, isl);
     const bool fin = env_finite(O);
@@ -445,25 +496,6 @@ cp_reset_kernel(cp_config cfg, Bufs b, float* obs_out) {
     b.ret_acc[il] = 0.0f;
 }
 
-// One env-step's action forces, action_force * action (bullet_cartpole.py:201-207): continuous
-// float4 (a00 a01 a10 a11) or discrete int8 x 2 through kDiscrete (out-of-range index = 0).
-template <int KIND>
-CP_DEV void action_forces(const void* actions, size_t row, real F, real f[4]) {
-    real a00, a01, a10, a11;
-    if constexpr (KIND == CP_ACTION_CONTINUOUS) {
-        const float4 a = reinterpret_cast<const float4*>(actions)[row];
-        a00 = a.x; a01 = a.y; a10 = a.z; a11 = a.w;
-    } else {
-        const char2 a = reinterpret_cast<const char2*>(actions)[row];
-        int k0 = a.x, k1 = a.y;
-        k0 = (k0 < 0 || k0 >= CP_NUM_DISCRETE) ? 0 : k0;
-        k1 = (k1 < 0 || k1 >= CP_NUM_DISCRETE) ? 0 : k1;
-        a00 = kDiscrete[k0][0]; a01 = kDiscrete[k0][1];
-        a10 = kDiscrete[k1][0]; a11 = kDiscrete[k1][1];
-    }
-    f[0] = a00 * F; f[1] = a01 * F; f[2] = a10 * F; f[3] = a11 * F;
-}
-
 // LAT: the latency shape of cp_reset_kernel<true> (1 wave per SIMD, 512 registers, fast-form
 // rows) for batches whose waves all get a SIMD of their own (<= 32,768 envs).  WIDE: the latency shape on
 // 16 lanes per env (cp_reset_kernel), for batches that leave most SIMDs idle.
@@ -474,6 +506,7 @@ cp_step_kernel(cp_config cfg, Bufs b, const void* actions, float* obs_out, float
                float* term_out, float* readback, int rb_bug, Lqr lq) {
     static_assert(!WIDE || (LAT && !PM && !SLP), "WIDE: latency shape, default contact model");
     constexpr int LW = WIDE ? WIDE : 2;  // lanes per env
+    constexpr bool KEEP = LAT && !kF64;  // late_mem
     __shared__ real lds_pool[(PM ? POOL_FLOATS_PM : POOL_FLOATS) * WAVE];
     const int B = cfg.num_envs;
     const int t = blockIdx.x * WAVE + threadIdx.x;
@@ -491,19 +524,6 @@ cp_step_kernel(cp_config cfg, Bufs b, const void* actions, float* obs_out, float
     bool want_reset = false;
     bool render_me = false;  // simulated this step: its frames go to the render kernel
     Stamps ST;
-    // the env index through an opaque register copy where the outputs are addressed after the substeps: the
-    // 64-bit per-lane addresses formed once at the top otherwise live through the substep loop (spilled: the
-    // step kernel's scratch frame, written at the top and read back at the end of every launch)
-    auto late_i = [&]() {
-        int x = i;
-        asm volatile("" : "+v"(x));
-        return x;
-    };
-    // the lane's island (lane parity) recomputed from the lane id where the late offsets need it (a kept copy
-    // and the island offsets derived from it were spilled)
-    auto late_isl = [&]() {
-        return (int)(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 1u);
-    };
     CP_STAMP(k0);
     CP_RT(r0);
     if (inb) {
@@ -539,27 +559,22 @@ cp_step_kernel(cp_config cfg, Bufs b, const void* actions, float* obs_out, float
             bool lqr_done = false;
             const float* K = nullptr;
             if constexpr (LQR) {
-                K = lq.gains + (lq.per_env ? (size_t)i * 32 : 0);
+                K = lqr_gains(lq, i);
                 lqr_observe(O, second, cfg, lq, K, u, nullptr);
             }
             for (int r = 0; r < R; ++r) {
                 for (int s = 0; s < SR; ++s) {
-                    // the throughput shape: the lane's SoA offsets rebuilt per substep from the opaque index (not live
-                    // through the loop; scratch 48 -> 24 B/lane); the 0-scratch latency kernels keep G (a lone wave
-                    // pays the rebuild: latency reset list +2.6 %)
-                    const Mem Gs = (LAT && !kF64) ? G : Mem::make(b.state, b.scratch, B, late_i(), late_isl(), b.pman);
-                    substep<LAT && !kF64, false, true, PM, SLP, WIDE>(O, cfg.phys, L, pool, pool0, ov, Gs, ST);
-                    if constexpr (LQR) {  // disturbance + control (:897-901), control from the pre-step state
-                        apply_force_link(O, fa + u[0], fb + u[1]);
+                    const Mem Gs = late_mem<KEEP>(G, b, B, i);
+                    substep<KEEP, false, true, PM, SLP, WIDE>(O, cfg.phys, L, pool, pool0, ov, Gs, ST);
+                    push_own_cart<LQR>(O, fa, fb, u);
+                    if constexpr (LQR) {  // the next control force, from this substep's state
                         float* s8 = (lq.state8 && owner) ? lq.state8 + (((size_t)i * R + r) * SR + s) * 16 : nullptr;
                         lqr_done |= lqr_observe(O, second, cfg, lq, K, u, s8);
-                    } else {
-                        apply_force_link(O, fa, fb);
                     }
                     if (readback) {  // 12-states of both poles: the whole env on both lanes (DPP), the lead writes
                         const Sim V = env_view(O);
                         if (lead) {
-                            float* rb = readback + (size_t)late_i() * 2 * R * SR * 12;
+                            float* rb = readback + (size_t)opaque_index(i) * 2 * R * SR * 12;
                             readback_pole<1, 1>(V, rb + ((size_t)(0 * R + r) * SR + s) * 12);
                             if (rb_bug) readback_pole<3, 1>(V, rb + ((size_t)(1 * R + r) * SR + s) * 12);
                             else readback_pole<3, 3>(V, rb + ((size_t)(1 * R + r) * SR + s) * 12);
@@ -569,22 +584,21 @@ cp_step_kernel(cp_config cfg, Bufs b, const void* actions, float* obs_out, float
                 if (lead) {
                     float row[14];
                     write_obs_row(O, row);
-                    float* orow = obs_out + ((size_t)late_i() * R + r) * 14;
+                    float* orow = obs_out + ((size_t)opaque_index(i) * R + r) * 14;
 #pragma unroll
                     for (int f = 0; f < 14; ++f) put_out(&orow[f], row[f]);
                 }
-                if (b.rposes && owner) write_rposes_own(O, isl, b.rposes + ((size_t)late_i() * R + r) * CP_NUM_DYN * 7);
+                if (b.rposes && owner)
+                    write_rposes_own(O, isl, b.rposes + ((size_t)opaque_index(i) * R + r) * CP_NUM_DYN * 7);
             }
             render_me = lead && b.rposes != nullptr;
             ov += (int)partner_u((uint32_t)ov);
-            const int il = late_i();
+            const int il = opaque_index(i);
             if (ov && lead) b.overflow[il] += ov;
-            const int isle = (LAT && !kF64) ? isl : late_isl();
-            const Mem Ge = (LAT && !kF64) ? G : Mem::make(b.state, b.scratch, B, il, isle, b.pman);
+            const int isle = KEEP ? isl : lane_island();
+            const Mem Ge = late_mem<KEEP, false>(G, b, B, il, isle);
             const int steps = ldi(Ge.st, CP_SF_STEPS, Ge.off) + 1;
-            bool done = steps >= cfg.max_episode_len;
-            if (cfg.done_on_bounds && bounds_exceeded(O, cfg)) done = true;
-            if (LQR && lqr_done) done = true;
+            const bool done = episode_over(steps, O, cfg, LQR && lqr_done);
             if (owner) store_own(O, Ge, isle);  // each lane stores its own island
             if constexpr (SLP) store_sleep(O, Ge, isle);
             const bool fin = env_finite(O);
@@ -668,9 +682,8 @@ cp_rollout_kernel(cp_config cfg, Bufs b, int K, const void* actions, float* obs_
     const Lane L = Lane::make(isl, cfg.phys);
     const SoaF term = SoaF::make(b.term_obs, B, R * 14);
     const size_t obs_step = (size_t)B * R * 14;
-    // the env index through an opaque register copy wherever the loop body forms an address: the
-    // 64-bit per-lane addresses are otherwise hoisted out of the substep loop and spilled
-    auto env = [&]() { uint32_t v = (uint32_t)i; asm volatile("" : "+v"(v)); return (size_t)v; };
+    // the opaque env index wherever the loop body forms an address (zero-extended: an env index is not negative)
+    auto env = [&]() { return (size_t)(uint32_t)opaque_index(i); };
     auto ldc = [&](int f) { return (int)to_bits(G.lx(f)); };
     auto stc = [&](int f, int v) { G.sx(f, bits_to<real>((uint32_t)v)); };
     auto ldu = [&](int f) { return G.lx(f); };
@@ -699,7 +712,7 @@ cp_rollout_kernel(cp_config cfg, Bufs b, int K, const void* actions, float* obs_
             flags |= RF_LAST_SIM;
             if constexpr (LQR) {
                 flags &= ~RF_LQR_DONE;
-                lqr_observe(O, second, cfg, lq, lq.gains + (lq.per_env ? (size_t)i * 32 : 0), u, nullptr);
+                lqr_observe(O, second, cfg, lq, lqr_gains(lq, i), u, nullptr);
                 G.sx(RC_U0, u[0]); G.sx(RC_U1, u[1]);
             }
         }
@@ -715,18 +728,15 @@ cp_rollout_kernel(cp_config cfg, Bufs b, int K, const void* actions, float* obs_
         int k = ldc(RC_K), sub = ldc(RC_SUB);
         uint32_t flags = (uint32_t)ldc(RC_FLAGS);
         if (!(flags & RF_RESETTING)) {
-            real f[4];
             const size_t e = env();
+            real f[4];
             action_forces<KIND>(actions, (size_t)k * B + e, real(cfg.action_force), f);
             const real fa = second ? f[2] : f[0], fb = second ? f[3] : f[1];  // the own cart's force
+            if constexpr (LQR) { u[0] = ldu(RC_U0); u[1] = ldu(RC_U1); }
+            push_own_cart<LQR>(O, fa, fb, u);
             if constexpr (LQR) {
-                u[0] = ldu(RC_U0); u[1] = ldu(RC_U1);
-                apply_force_link(O, fa + u[0], fb + u[1]);
-                if (lqr_observe(O, second, cfg, lq, lq.gains + (lq.per_env ? (size_t)i * 32 : 0), u, nullptr))
-                    flags |= RF_LQR_DONE;
+                if (lqr_observe(O, second, cfg, lq, lqr_gains(lq, i), u, nullptr)) flags |= RF_LQR_DONE;
                 G.sx(RC_U0, u[0]); G.sx(RC_U1, u[1]);
-            } else {
-                apply_force_link(O, fa, fb);
             }
             ++sub;
             float* obs = obs_out + (size_t)k * obs_step + e * R * 14;
@@ -745,9 +755,7 @@ cp_rollout_kernel(cp_config cfg, Bufs b, int K, const void* actions, float* obs_
             // step end (the step kernel's epilogue)
             const int steps = ldc(RC_STEPS) + 1;
             const int episode = ldc(RC_EPISODE);
-            bool done = steps >= cfg.max_episode_len;
-            if (cfg.done_on_bounds && bounds_exceeded(O, cfg)) done = true;
-            if (LQR && (flags & RF_LQR_DONE)) done = true;
+            const bool done = episode_over(steps, O, cfg, LQR && (flags & RF_LQR_DONE));
             const float ret = __uint_as_float(to_bits(G.lx(RC_RET))) + 1.0f;
             const bool fin = env_finite(O);
             if (lead) {

@@ -252,6 +252,35 @@ static int check(cp_handle* h, hipError_t e, const char* what) {
 
 static inline unsigned grid_for(int n, int block) { return (unsigned)((n + block - 1) / block); }
 
+static inline size_t real_bytes(const cp_handle* h) { return h->f64 ? sizeof(double) : sizeof(float); }  // of `real`
+// launch() on `st` inside timing_slot's event pair for `kind`, when it gives one; a launch error goes under `what`
+template <typename F>
+static int timed_launch(cp_handle* h, int kind, hipStream_t st, const char* what, F launch) {
+    hipEvent_t* ev = timing_slot(h, kind);
+    if (ev) CP_TRY(h, hipEventRecord(ev[0], st));
+    launch();
+    if (check(h, hipGetLastError(), what)) return -1;
+    if (ev) CP_TRY(h, hipEventRecord(ev[1], st));
+    return 0;
+}
+
+// CP_AUTORESET_NEXT_STEP: make `st` wait for the reset in flight on a side stream (every entry point
+// that reads or writes the state or the per-env outputs of the last call does this first)
+static int join_next_step(cp_handle* h, hipStream_t st) {
+    if (h->cfg.autoreset == CP_AUTORESET_NEXT_STEP && h->ninflight >= 0)
+        CP_TRY(h, hipStreamWaitEvent(st, h->njoin[h->ninflight], 0));
+    return 0;
+}
+
+// a device-to-device copy between a buffer of handle h (not null) and the caller's, behind any NEXT_STEP reset in flight
+static int copy_d2d(cp_handle* h, const char* who, void* dst, const void* src, size_t bytes, void* stream) {
+    if (!dst || !src) return fail(h, std::string(who) + ": null argument");
+    CP_TRY(h, hipSetDevice(h->device));
+    if (join_next_step(h, (hipStream_t)stream)) return -1;
+    CP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
 extern "C" {
 
 int cp_abi_version(void) { return CP_ABI_VERSION; }
@@ -396,7 +425,7 @@ int cp_create(const cp_config* cfg, int device, cp_handle** out) {
         if (e != hipSuccess) return fail_free(e, "hipMalloc " #ptr); \
         if (zero) zeros.push_back({(ptr), (bytes)});                 \
     } while (0)
-    const size_t rb = h->f64 ? sizeof(double) : sizeof(float);  // bytes of the handle's real type
+    const size_t rb = real_bytes(h);
     CP_ALLOC(h->b.state, (size_t)CP_STATE_FIELDS * B * rb, false);
     CP_ALLOC(h->b.term_obs, (size_t)R * 14 * B * sizeof(float), true);
     CP_ALLOC(h->b.bumps, B * (size_t)(cfg->initial_force_steps > 0 ? cfg->initial_force_steps : 1) * 4 * rb, true);
@@ -479,10 +508,8 @@ void cp_destroy(cp_handle* h) {
 
 // raster obs of the envs in list[0 .. *count) (a device count: the grid covers B).  launch = false only
 // names the kernel the handle would launch (cp_render_kernel_name): 0 small2, 1 small, 2 wave kernel.
-static int launch_render(cp_handle* h, const int32_t* list, const int32_t* count, hipStream_t st,
-                         bool launch = true, int* kind = nullptr) {
-    hipEvent_t* ev = launch ? timing_slot(h, 2) : nullptr;
-    if (ev) CP_TRY(h, hipEventRecord(ev[0], st));
+static void render_dispatch(cp_handle* h, const int32_t* list, const int32_t* count, hipStream_t st, bool launch,
+                            int* kind) {
     const int C = h->raster.num_cameras, R = h->cfg.action_repeats, npx = h->raster.width * h->raster.height;
     const uint8_t* cls = launch ? reinterpret_cast<const uint8_t*>(h->b.rtable + (size_t)C * npx) : nullptr;
     const size_t small = (size_t)cp::render_small_lds(C, R, npx).total;
@@ -508,7 +535,6 @@ static int launch_render(cp_handle* h, const int32_t* list, const int32_t* count
         if (kind) *kind = 0;  // launched
     } else if (!launch) {
         if (kind) *kind = small <= (size_t)cp::SMALL_LDS_MAX ? 1 : 2;
-        return 0;
     } else if (small <= (size_t)cp::SMALL_LDS_MAX) {  // one block per env, dense ray tests
         hipLaunchKernelGGL(cp::cp_render_small_kernel, dim3((unsigned)h->cfg.num_envs),
                            dim3(cp::RENDER_WAVES * cp::WAVE_R), small, st, h->raster, h->cfg.phys, R, list, count,
@@ -519,16 +545,16 @@ static int launch_render(cp_handle* h, const int32_t* list, const int32_t* count
         hipLaunchKernelGGL(cp::cp_render_kernel, dim3(grid), dim3(cp::RENDER_WAVES * cp::WAVE_R), lds, st, h->raster,
                            h->cfg.phys, R, list, count, h->b.rposes, h->b.rtable, cls, h->pixels);
     }
-    if (!launch) return 0;
-    if (check(h, hipGetLastError(), "cp_render_kernel")) return -1;
-    if (ev) CP_TRY(h, hipEventRecord(ev[1], st));
-    return 0;
+}
+
+static int launch_render(cp_handle* h, const int32_t* list, const int32_t* count, hipStream_t st) {
+    return timed_launch(h, 2, st, "cp_render_kernel", [&] { render_dispatch(h, list, count, st, true, nullptr); });
 }
 
 const char* cp_render_kernel_name(cp_handle* h) {
     if (!h || !h->pixels) return nullptr;
     int kind = -1;
-    if (launch_render(h, nullptr, nullptr, nullptr, false, &kind) != 0) return nullptr;
+    render_dispatch(h, nullptr, nullptr, nullptr, false, &kind);
     static const char* const names[3] = {"cp_render_small2_kernel", "cp_render_small_kernel", "cp_render_kernel"};
     return kind >= 0 && kind < 3 ? names[kind] : nullptr;
 }
@@ -540,13 +566,17 @@ static void use_counter(cp_handle* h) {
     h->par ^= 1;
 }
 
+static int launch_step_timed(cp_handle* h, const cpc::Bufs& b, const void* actions, int action_kind, float* obs_out,
+                             float* reward_out, uint8_t* done_out, float* terminal_obs_out, hipStream_t st) {
+    return timed_launch(h, 0, st, "cp_step_kernel", [&] {
+        CP_LAUNCH(h, launch_step, h->step_shape, action_kind, h->cfg, b, actions, obs_out, reward_out, done_out,
+                  terminal_obs_out, h->readback, h->readback_bug, h->lqr, st);
+    });
+}
+
 static int launch_reset_list(cp_handle* h, const cpc::Bufs& b, float* obs_out, hipStream_t st) {
-    hipEvent_t* ev = timing_slot(h, 1);
-    if (ev) CP_TRY(h, hipEventRecord(ev[0], st));
-    CP_LAUNCH(h, launch_reset, h->reset_shape, h->cfg, b, obs_out, st);
-    if (check(h, hipGetLastError(), "cp_reset_kernel")) return -1;
-    if (ev) CP_TRY(h, hipEventRecord(ev[1], st));
-    return 0;
+    return timed_launch(h, 1, st, "cp_reset_kernel",
+                        [&] { CP_LAUNCH(h, launch_reset, h->reset_shape, h->cfg, b, obs_out, st); });
 }
 
 // A graph replays a captured call any number of times without the host seeing it, so once any entry
@@ -578,14 +608,6 @@ static int launch_reset_from_list(cp_handle* h, float* obs_out, hipStream_t st, 
     return 0;
 }
 
-// CP_AUTORESET_NEXT_STEP: make `st` wait for the reset in flight on a side stream (every entry point
-// that reads or writes the state or the per-env outputs of the last call does this first)
-static int join_next_step(cp_handle* h, hipStream_t st) {
-    if (h->cfg.autoreset == CP_AUTORESET_NEXT_STEP && h->ninflight >= 0)
-        CP_TRY(h, hipStreamWaitEvent(st, h->njoin[h->ninflight], 0));
-    return 0;
-}
-
 // cp_step of a NEXT_STEP handle.  Call n appends its finishing envs to list q = n % 2
 // (their done field becomes 2 + q) and starts their reset on side stream q as soon as its step kernel
 // is done; call n + 1 steps every other env meanwhile (the step kernel skips done fields >= 2), then
@@ -600,12 +622,7 @@ static int step_next_step(cp_handle* h, const void* actions, int action_kind, fl
     b.count_next = nullptr;
     b.npar = q;
     b.keep_done = 1;
-    hipEvent_t* ev = timing_slot(h, 0);
-    if (ev) CP_TRY(h, hipEventRecord(ev[0], st));
-    CP_LAUNCH(h, launch_step, h->step_shape, action_kind, h->cfg, b, actions, obs_out, reward_out, done_out,
-              terminal_obs_out, h->readback, h->readback_bug, h->lqr, st);
-    CP_TRY(h, hipGetLastError());
-    if (ev) CP_TRY(h, hipEventRecord(ev[1], st));
+    if (launch_step_timed(h, b, actions, action_kind, obs_out, reward_out, done_out, terminal_obs_out, st)) return -1;
     CP_TRY(h, hipEventRecord(h->nfork[q], st));
     if (h->ninflight >= 0) {  // the previous call's list: its reset obs are this call's obs
         const int p = h->ninflight;
@@ -661,12 +678,7 @@ int cp_step(cp_handle* h, const void* actions, int action_kind, float* obs_out, 
     const bool capturing = note_capture(h, st);
     const bool reset = h->cfg.autoreset && may_finish(h, st);
     if (h->pixels) CP_TRY(h, hipMemsetAsync(h->b.rcount, 0, sizeof(int32_t), st));
-    hipEvent_t* ev = timing_slot(h, 0);
-    if (ev) CP_TRY(h, hipEventRecord(ev[0], st));
-    CP_LAUNCH(h, launch_step, h->step_shape, action_kind, h->cfg, h->b, actions, obs_out, reward_out, done_out,
-              terminal_obs_out, h->readback, h->readback_bug, h->lqr, st);
-    CP_TRY(h, hipGetLastError());
-    if (ev) CP_TRY(h, hipEventRecord(ev[1], st));
+    if (launch_step_timed(h, h->b, actions, action_kind, obs_out, reward_out, done_out, terminal_obs_out, st)) return -1;
     // autoreset envs were simulated this step, so they are in the render list; the reset
     // kernel rewrites their poses first, and the one render launch draws the new episode
     if (reset && launch_reset_from_list(h, obs_out, st, false)) return -1;
@@ -691,12 +703,11 @@ int cp_rollout(cp_handle* h, int steps, const void* actions, int action_kind, fl
         return fail(h, "cp_rollout: CP_AUTORESET_NEXT_STEP handles step through cp_step only");
     hipStream_t st = (hipStream_t)stream;
     CP_TRY(h, hipSetDevice(h->device));
-    hipEvent_t* ev = timing_slot(h, 0);
-    if (ev) CP_TRY(h, hipEventRecord(ev[0], st));
-    CP_LAUNCH(h, launch_rollout, h->step_shape, action_kind, h->cfg, h->b, steps, actions, obs_out, reward_out, done_out,
-              terminal_obs_out, h->lqr, st);
-    CP_TRY(h, hipGetLastError());
-    if (ev) CP_TRY(h, hipEventRecord(ev[1], st));
+    if (timed_launch(h, 0, st, "cp_rollout_kernel", [&] {
+            CP_LAUNCH(h, launch_rollout, h->step_shape, action_kind, h->cfg, h->b, steps, actions, obs_out, reward_out,
+                      done_out, terminal_obs_out, h->lqr, st);
+        }))
+        return -1;
     note_capture(h, st);
     if (h->phase >= 0) h->phase += steps;  // the kernel resets finishing envs inline
     return 0;
@@ -841,10 +852,7 @@ int cp_set_policy_noise(cp_handle* h, const cp_policy_noise* p) {
 int cp_policy_noise_get(cp_handle* h, float* out, void* stream) {
     if (!h || !out) return fail(h, "cp_policy_noise_get: null argument");
     if (!h->pol.noise_state) return fail(h, "cp_policy_noise_get: no noise has been set (cp_set_policy_noise)");
-    CP_TRY(h, hipSetDevice(h->device));
-    CP_TRY(h, hipMemcpyAsync(out, h->pol.noise_state, (size_t)h->cfg.num_envs * 4 * sizeof(float), hipMemcpyDeviceToDevice,
-                             (hipStream_t)stream));
-    return 0;
+    return copy_d2d(h, "cp_policy_noise_get", out, h->pol.noise_state, (size_t)h->cfg.num_envs * 4 * sizeof(float), stream);
 }
 
 int cp_policy_noise_set(cp_handle* h, const float* in, void* stream) {
@@ -915,7 +923,7 @@ int cp_set_bump_forces64(cp_handle* h, const double* forces, void* stream) {
 
 int64_t cp_state_bytes(const cp_handle* h) {
     if (!h) return fail(nullptr, "cp_state_bytes: null handle");
-    return (int64_t)CP_STATE_FIELDS * h->cfg.num_envs * (h->f64 ? (int64_t)sizeof(double) : (int64_t)sizeof(float));
+    return (int64_t)CP_STATE_FIELDS * h->cfg.num_envs * (int64_t)real_bytes(h);
 }
 
 int cp_set_kernel_shape(cp_handle* h, int step_shape, int reset_shape) {
@@ -936,37 +944,28 @@ int cp_get_kernel_shape(const cp_handle* h, int* step_shape, int* reset_shape) {
 }
 
 int cp_get_state(cp_handle* h, void* state_out, void* stream) {
-    if (!h || !state_out) return fail(h, "cp_get_state: null argument");
-    CP_TRY(h, hipSetDevice(h->device));
-    if (join_next_step(h, (hipStream_t)stream)) return -1;
-    size_t n = (size_t)CP_STATE_FIELDS * h->cfg.num_envs;
-    CP_TRY(h, hipMemcpyAsync(state_out, h->b.state, n * (h->f64 ? sizeof(double) : sizeof(float)), hipMemcpyDeviceToDevice,
-                             (hipStream_t)stream));
-    return 0;
+    if (!h) return fail(h, "cp_get_state: null argument");
+    return copy_d2d(h, "cp_get_state", state_out, h->b.state, (size_t)cp_state_bytes(h), stream);
 }
 
 int cp_set_state(cp_handle* h, const void* state_in, void* stream) {
-    if (!h || !state_in) return fail(h, "cp_set_state: null argument");
-    CP_TRY(h, hipSetDevice(h->device));
-    if (join_next_step(h, (hipStream_t)stream)) return -1;
-    size_t n = (size_t)CP_STATE_FIELDS * h->cfg.num_envs;
-    CP_TRY(h, hipMemcpyAsync(h->b.state, state_in, n * (h->f64 ? sizeof(double) : sizeof(float)), hipMemcpyDeviceToDevice,
-                             (hipStream_t)stream));
+    if (!h) return fail(h, "cp_set_state: null argument");
+    if (copy_d2d(h, "cp_set_state", h->b.state, state_in, (size_t)cp_state_bytes(h), stream)) return -1;
     h->phase = -1;  // step counters of any value
     // the persistent manifolds are not part of the state SoA: no cached contact survives a teleport
     // (as in the reset kernel), so the next step rebuilds them from the new poses
     if (h->b.pman)
         CP_TRY(h, hipMemsetAsync(h->b.pman, 0, (size_t)CP_PM_FIELDS * 2 * h->cfg.num_envs *
-                                                   (h->f64 ? sizeof(double) : sizeof(float)), (hipStream_t)stream));
+                                                   real_bytes(h), (hipStream_t)stream));
     return 0;
 }
 
 int cp_episode_returns(cp_handle* h, float* returns_out, int32_t* lengths_out, void* stream) {
     if (!h) return fail(h, "cp_episode_returns: null handle");
     CP_TRY(h, hipSetDevice(h->device));
-    if (join_next_step(h, (hipStream_t)stream)) return -1;
-    size_t B = (size_t)h->cfg.num_envs;
     hipStream_t st = (hipStream_t)stream;
+    if (join_next_step(h, st)) return -1;
+    const size_t B = (size_t)h->cfg.num_envs;
     if (returns_out) CP_TRY(h, hipMemcpyAsync(returns_out, h->b.last_ret, B * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (lengths_out)
         CP_TRY(h, hipMemcpyAsync(lengths_out, h->b.last_len, B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
@@ -974,21 +973,13 @@ int cp_episode_returns(cp_handle* h, float* returns_out, int32_t* lengths_out, v
 }
 
 int cp_nonfinite_counts(cp_handle* h, int32_t* out, void* stream) {
-    if (!h || !out) return fail(h, "cp_nonfinite_counts: null argument");
-    CP_TRY(h, hipSetDevice(h->device));
-    if (join_next_step(h, (hipStream_t)stream)) return -1;
-    CP_TRY(h, hipMemcpyAsync(out, h->b.nonfinite, (size_t)h->cfg.num_envs * sizeof(int32_t), hipMemcpyDeviceToDevice,
-                             (hipStream_t)stream));
-    return 0;
+    if (!h) return fail(h, "cp_nonfinite_counts: null argument");
+    return copy_d2d(h, "cp_nonfinite_counts", out, h->b.nonfinite, (size_t)h->cfg.num_envs * sizeof(int32_t), stream);
 }
 
 int cp_overflow_counts(cp_handle* h, int32_t* out, void* stream) {
-    if (!h || !out) return fail(h, "cp_overflow_counts: null argument");
-    CP_TRY(h, hipSetDevice(h->device));
-    if (join_next_step(h, (hipStream_t)stream)) return -1;
-    CP_TRY(h, hipMemcpyAsync(out, h->b.overflow, (size_t)h->cfg.num_envs * sizeof(int32_t), hipMemcpyDeviceToDevice,
-                             (hipStream_t)stream));
-    return 0;
+    if (!h) return fail(h, "cp_overflow_counts: null argument");
+    return copy_d2d(h, "cp_overflow_counts", out, h->b.overflow, (size_t)h->cfg.num_envs * sizeof(int32_t), stream);
 }
 
 int cp_debug_stamps(cp_handle* h, uint64_t* out64, int reset) {

@@ -114,6 +114,74 @@ def test_rollout_lqr_policy_and_step_after_done(shape):
     assert d[12:].all() and not d[:11].any()     # steps after done return the last obs, done 1
 
 
+# The cp_rollout_kernel variants (precision x contact model x action kind x LQR x shape) that no test above or in
+# the models' own files launches; cp_step on the twin handle launches the cp_step_kernel and cp_reset_kernel of the
+# same variant.  Launched elsewhere: fp32 default model, discrete and continuous on both shapes, continuous LQR on
+# both shapes (above).  The fp32 persistent and sleeping discrete rollouts (test_gpu_persistent.py,
+# test_gpu_sleeping.py: obs, done and state only) and the fp64 discrete rollout (test_gpu_reset_skip.py: against
+# another rollout only) are launched elsewhere, and are here for the whole comparison against cp_step.  (The
+# sleeping model has no LQR; fp64 and the two models have the latency shape only.)
+PM, SLP = abi.CP_MODEL_PERSISTENT, abi.CP_MODEL_SLEEPING
+ROLLOUT_VARIANTS = {
+    # id: (precision, model_flags, continuous, lqr, shape)
+    "f32-discrete-lqr-tp": ("f32", 0, False, True, ("throughput", "throughput")),
+    "f32-discrete-lqr-lat": ("f32", 0, False, True, ("latency", "latency")),
+    "f32-pm-discrete": ("f32", PM, False, False, None),
+    "f32-pm-continuous": ("f32", PM, True, False, None),
+    "f32-pm-continuous-lqr": ("f32", PM, True, True, None),
+    "f32-pm-discrete-lqr": ("f32", PM, False, True, None),
+    "f32-slp-discrete": ("f32", SLP, False, False, None),
+    "f32-slp-continuous": ("f32", SLP, True, False, None),
+    "f64-discrete": ("f64", 0, False, False, None),
+    "f64-continuous": ("f64", 0, True, False, None),
+    "f64-continuous-lqr": ("f64", 0, True, True, None),
+    "f64-discrete-lqr": ("f64", 0, False, True, None),
+    "f64-pm-discrete": ("f64", PM, False, False, None),
+    "f64-pm-continuous": ("f64", PM, True, False, None),
+    "f64-pm-continuous-lqr": ("f64", PM, True, True, None),
+    "f64-pm-discrete-lqr": ("f64", PM, False, True, None),
+    "f64-slp-discrete": ("f64", SLP, False, False, None),
+    "f64-slp-continuous": ("f64", SLP, True, False, None),
+}
+
+
+@pytest.mark.parametrize("autoreset", [1, 0], ids=["autoreset", "no-autoreset"])
+@pytest.mark.parametrize("variant", list(ROLLOUT_VARIANTS))
+def test_rollout_variant_equals_steps(variant, autoreset):
+    """B = 33: a full wave and a wave with one live lane pair (the i >= B exits, the ballots of a mostly dead
+    wave).  Episodes of 12 steps in K = 30: with autoreset every env finishes, runs the 130-substep inline reset
+    and steps on, twice; without it steps 12 to 29 are step-after-done replays."""
+    precision, model, continuous, lqr, shape = ROLLOUT_VARIANTS[variant]
+    B, K, L = 33, 30, 12
+    hs = []
+    for _ in range(2):
+        cfg = native.default_config(num_envs=B, action_repeats=2, steps_per_repeat=1, initial_force=55.0, seed=19,
+                                    autoreset=autoreset, max_episode_len=L)
+        cfg.phys.model_flags = model
+        cfg.precision = abi.CP_PRECISION_F64 if precision == "f64" else abi.CP_PRECISION_F32
+        h = BatchedCartpole(B, 0, config=cfg)
+        if shape:
+            h.set_kernel_shape(*shape)
+        if lqr:
+            h.enable_lqr(torch.from_numpy(exact_gains()), state8=False, done_pos=3.0, done_angle=float(np.pi / 4))
+        h.reset()
+        hs.append(h)
+    roll, step_env = hs
+    rng = np.random.default_rng(6)
+    if continuous:
+        acts = torch.from_numpy(rng.uniform(-1, 1, (K, B, 2, 2)).astype(np.float32)).cuda()
+    else:
+        acts = torch.from_numpy(rng.integers(0, 5, (K, B, 2)).astype(np.int8)).cuda()
+    d = _compare(roll, step_env, acts, variant)
+    _assert_same(_np(roll.overflow_counts()), _np(step_env.overflow_counts()), variant + " overflow counts")
+    if autoreset:
+        assert (d.sum(0) >= 2).all() and roll.rollout_terminal_obs is not None
+    else:
+        assert d[L:].all() and roll.rollout_terminal_obs is None
+    for h in hs:
+        h.close()
+
+
 def test_rollout_rejects_side_outputs():
     env = BatchedCartpole(16, 0, action_repeats=2)
     env.reset()
