@@ -204,6 +204,23 @@ class cp_policy_noise(C.Structure):
     ]
 
 
+# ---- seeded ES perturbations of the policy's centre (include/cartpole_amd.h: cp_policy_es)
+CP_ES_OFF, CP_ES_BYTES4 = range(2)
+CP_ES_ANTITHETIC = 0x1
+
+
+class cp_policy_es(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("flags", C.c_int32),
+        ("sigma", C.c_float),
+        ("generation", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("population", C.c_int32),
+        ("group", C.c_int32),
+    ]
+
+
 def pixels_shape(B, H, W, C_, R):
     """Raster obs per env (H, W, 3, C, R), bullet_cartpole.py:299-306 (camera before repeat)."""
     return (B, H, W, 3, C_, R)

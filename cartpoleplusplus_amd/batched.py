@@ -105,6 +105,7 @@ class BatchedCartpole:
         self.readback = None
         self.pixels = None
         self.policy = self.policy_weights = None   # set_policy
+        self.policy_es = None                      # set_policy_es
 
     # -------------------------------------------------------------- plumbing
     def _stream(self):
@@ -362,6 +363,50 @@ class BatchedCartpole:
         if x is not None:
             x = _device_buffer(x, (self.B, 2, 2), torch.float32, self.device, "policy noise")
         native.check(self.h, self.lib.cp_policy_noise_set(self.h, _ptr(x), self._stream()), "cp_policy_noise_set")
+
+    def set_policy_es(self, population, sigma=0.0, group=1, seed=0, generation=0, antithetic=True):
+        """Seeded ES perturbations (cp_set_policy_es): set_policy()'s one weight set becomes the centre theta,
+        and env i acts with member m = ((env_id_offset + i) // group) % population, whose weights
+        theta + s * sigma * eps(seed, generation, m) the kernel forms as it stages them: no (P, F) buffer and no
+        noise tensors.  antithetic: members 2k and 2k+1 share eps with signs + and -.  Bump `generation` once
+        per ES iteration; policy_es_gradient() draws the same eps again for the update.  population None turns
+        ES off."""
+        if population is None:
+            native.check(self.h, self.lib.cp_set_policy_es(self.h, None), "cp_set_policy_es")
+            self.policy_es = None
+            return
+        p = abi.cp_policy_es()
+        p.kind, p.flags = abi.CP_ES_BYTES4, abi.CP_ES_ANTITHETIC if antithetic else 0
+        p.sigma, p.generation, p.seed = float(sigma), int(generation) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF
+        p.population, p.group = int(population), int(group)
+        native.check(self.h, self.lib.cp_set_policy_es(self.h, C.byref(p)), "cp_set_policy_es")
+        self.policy_es = p
+
+    def _es_range(self, lo, count):
+        if self.policy_es is None or self.policy is None:
+            raise native.CartpoleError("ES perturbations need set_policy() and set_policy_es()")
+        return int(lo), int(self.policy_es.population - lo if count is None else count), \
+            int(self.lib.cp_policy_floats(C.byref(self.policy)))
+
+    def policy_es_weights(self, lo=0, count=None):
+        """(count, F) float32: the packed weights of the members lo .. lo + count - 1 (default: all from lo on)
+        as policy_act() forms them (cp_policy_es_weights); policy.unpack-able rows, e.g. to checkpoint the best."""
+        lo, count, F = self._es_range(lo, count)
+        out = torch.empty((max(count, 0), F), device=self.device, dtype=torch.float32)
+        native.check(self.h, self.lib.cp_policy_es_weights(self.h, lo, count, _ptr(out), self._stream()),
+                     "cp_policy_es_weights")
+        return out
+
+    def policy_es_gradient(self, coeff, lo=0):
+        """(F,) float32: sum_m coeff[m - lo] * s(m) * eps(m) over the members lo .. lo + len(coeff) - 1, eps drawn
+        again instead of kept (cp_policy_es_gradient); deterministic.  The ES update is
+        theta += lr / (P * sigma) * policy_es_gradient(fitness)."""
+        c = torch.as_tensor(coeff, dtype=torch.float32, device=self.device).contiguous().reshape(-1)
+        lo, count, F = self._es_range(lo, c.numel())
+        g = torch.empty((F,), device=self.device, dtype=torch.float32)
+        native.check(self.h, self.lib.cp_policy_es_gradient(self.h, lo, count, _ptr(c), _ptr(g), self._stream()),
+                     "cp_policy_es_gradient")
+        return g
 
     def set_bump_forces(self, forces):
         """Parity mode (bump_mode='host'): LINK-frame bump forces (B, 30, 2, 2).  float64 input goes

@@ -155,6 +155,17 @@ struct Pol {
     float* noise_state;    // [B][4]: the OU state x, or the last Gaussian draw
 };
 
+// seeded ES perturbations (cp_set_policy_es, cp_policy.h): the caller's cp_policy_es fields.  An argument of its
+// own for the ES kernels only, so Pol and the other kernels' arguments stay as they are.
+struct PolEs {
+    int32_t kind, flags;   // CP_ES_*; OFF: cp_policy_act runs the kernels of cps::policy_path
+    float sigma;
+    uint32_t generation;
+    uint64_t seed;
+    int32_t population;    // P, G: env i reads member ((env_id_offset + i) / G) % P
+    int32_t group;
+};
+
 // Per-handle device buffers.  `state` and `scratch` hold the handle's real type.
 struct Bufs {
     void* state;       // [CP_STATE_FIELDS][B] real
@@ -207,5 +218,12 @@ CP_DECLARE_LAUNCHES(cp)
 CP_DECLARE_LAUNCHES(cp64)
 // the MLP policy's kernels exist in fp32 only (cp_kernels.hip defines CP_POLICY)
 namespace cp {
-hipError_t launch_policy_act(int kind, const cp_config& cfg, const cpc::Bufs& b, const cpc::Pol& pol, hipStream_t st);
+hipError_t launch_policy_act(int kind, const cp_config& cfg, const cpc::Bufs& b, const cpc::Pol& pol,
+                             const cpc::PolEs& es, hipStream_t st);
+// cp_policy_es_weights / _gradient: members [lo, lo + count) of es over the centre theta [F]
+constexpr int kEsSlices = 64;  // the gradient's member slices: partial [kEsSlices][F], summed in slice order
+void launch_policy_es_weights(const cpc::PolEs& es, const float* theta, int F, int64_t lo, int count, float* out,
+                              hipStream_t st);
+void launch_policy_es_gradient(const cpc::PolEs& es, int F, int64_t lo, int count, const float* coeff, float* partial,
+                               float* grad, hipStream_t st);
 }

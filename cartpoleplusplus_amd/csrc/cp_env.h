@@ -984,14 +984,26 @@ void launch_rollout(int shape, int kind, const cp_config& cfg, const Bufs& b, in
 #ifdef CP_POLICY  // the fp32 translation unit only
 // cp_policy_act's kernel by cps::policy_path: the lane-per-env kernel (one weight set, or one member per wave), or
 // one member run's chunk per wave with the chunk's tiles and a layer's weights in dynamic LDS
-hipError_t launch_policy_act(int kind, const cp_config& cfg, const Bufs& b, const cpc::Pol& pol, hipStream_t st) {
+hipError_t launch_policy_act(int kind, const cp_config& cfg, const Bufs& b, const cpc::Pol& pol, const cpc::PolEs& es,
+                             hipStream_t st) {
     const cps::PolicyPath path = cps::policy_path(pol.population, pol.group, cfg.env_id_offset);
     const dim3 block(WAVE);
     auto by_kind = [&](auto cont, auto disc, dim3 grid, size_t lds, auto... args) {
         if (kind == CP_ACTION_CONTINUOUS) hipLaunchKernelGGL(cont, grid, block, lds, st, cfg, b, pol, args...);
         else hipLaunchKernelGGL(disc, grid, block, lds, st, cfg, b, pol, args...);
     };
-    if (path == cps::POLICY_MEMBER) {
+    if (es.kind != CP_ES_OFF) {  // seeded ES: the member path on the ES struct's P and G, whatever they are
+        const cps::PolicyRuns runs = cps::policy_runs(cfg.env_id_offset, es.group, cfg.num_envs);
+        const size_t lds = cps::policy_member_lds_bytes(pol.width, pol.num_layers, es.group, cfg.num_envs);
+        if (lds > 64 * 1024) {
+            const void* f = kind == CP_ACTION_CONTINUOUS ? (const void*)cp_policy_es_kernel<CP_ACTION_CONTINUOUS>
+                                                         : (const void*)cp_policy_es_kernel<CP_ACTION_DISCRETE>;
+            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        by_kind(cp_policy_es_kernel<CP_ACTION_CONTINUOUS>, cp_policy_es_kernel<CP_ACTION_DISCRETE>,
+                dim3((unsigned)runs.runs * (unsigned)runs.chunks_per_run), lds, es, runs);
+    } else if (path == cps::POLICY_MEMBER) {
         const cps::PolicyRuns runs = cps::policy_runs(cfg.env_id_offset, pol.group, cfg.num_envs);
         const size_t lds = cps::policy_member_lds_bytes(pol.width, pol.num_layers, pol.group, cfg.num_envs);
         if (lds > 64 * 1024) {  // above the default dynamic-LDS limit (widest layers with 64-env chunks: 136 KiB)
@@ -1010,6 +1022,25 @@ hipError_t launch_policy_act(int kind, const cp_config& cfg, const Bufs& b, cons
                 dim3(env_grid(cfg.num_envs, WAVE)), 0);
     }
     return hipSuccess;
+}
+
+void launch_policy_es_weights(const cpc::PolEs& es, const float* theta, int F, int64_t lo, int count, float* out,
+                              hipStream_t st) {
+    const int64_t threads = (int64_t)count * ((F + 3) >> 2);
+    hipLaunchKernelGGL(cp_policy_es_weights_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, es, theta,
+                       F, lo, count, out);
+}
+
+// the members' draws cut into at most kEsSlices slices (grid.y), then the slices summed in order
+void launch_policy_es_gradient(const cpc::PolEs& es, int F, int64_t lo, int count, const float* coeff, float* partial,
+                               float* grad, hipStream_t st) {
+    const int64_t hi = lo + count;
+    const int64_t draws = (es.flags & CP_ES_ANTITHETIC) ? ((hi + 1) >> 1) - (lo >> 1) : (int64_t)count;
+    const int slices = (int)(draws < kEsSlices ? draws : kEsSlices);
+    hipLaunchKernelGGL(cp_policy_es_gradient_kernel, dim3((unsigned)(((F + 3) / 4 + 255) / 256), (unsigned)slices),
+                       dim3(256), 0, st, es, F, lo, count, coeff, partial);
+    hipLaunchKernelGGL(cp_policy_es_reduce_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, F, slices, partial,
+                       grad);
 }
 #endif  // CP_POLICY
 

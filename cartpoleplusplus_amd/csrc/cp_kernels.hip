@@ -156,6 +156,9 @@ struct cp_handle {
     cpc::Lqr lqr{};
     cpc::Pol pol{};    // the MLP policy (cp_set_policy): the caller's fields and the handle's scratch
     bool pol_on = false;
+    cpc::PolEs es{};   // seeded ES perturbations (cp_set_policy_es); kind CP_ES_OFF: off
+    float* es_partial = nullptr;   // cp_policy_es_gradient's slices [kEsSlices][es_partial_floats]
+    int64_t es_partial_floats = 0;
     cp_timing timing;
     cp_raster_config raster{};
     uint16_t* pixels = nullptr;  // raster obs output (NULL: raster off)
@@ -496,6 +499,7 @@ void cp_destroy(cp_handle* h) {
     (void)hipFree(h->b.scratch);
     (void)hipFree(h->pol.scratch);
     (void)hipFree(h->pol.noise_state);
+    (void)hipFree(h->es_partial);
     (void)hipFree(h->b.stamps);
     (void)hipFree(h->b.stepped);
     (void)hipFree(h->b.pman);
@@ -739,6 +743,21 @@ static int64_t policy_floats(cp_handle* h, const cp_policy* p, const char* who) 
 
 int64_t cp_policy_floats(const cp_policy* p) { return policy_floats(nullptr, p, "cp_policy_floats"); }
 
+// cp_policy_es_gradient's scratch for the policy's F, (re)allocated by whichever of cp_set_policy and
+// cp_set_policy_es completes the pair (the calls themselves allocate nothing)
+static int es_scratch(cp_handle* h, const char* who) {
+    if (h->es.kind == CP_ES_OFF || !h->pol_on || h->pol.floats <= h->es_partial_floats) return 0;
+    CP_TRY(h, hipSetDevice(h->device));
+    float* s = nullptr;
+    if (hipMalloc((void**)&s, (size_t)cp::kEsSlices * h->pol.floats * sizeof(float)) != hipSuccess)
+        return fail(h, std::string(who) + ": out of device memory for the ES gradient's scratch");
+    CP_TRY(h, hipDeviceSynchronize());  // a gradient in flight may still read the old one
+    (void)hipFree(h->es_partial);
+    h->es_partial = s;
+    h->es_partial_floats = h->pol.floats;
+    return 0;
+}
+
 int cp_set_policy(cp_handle* h, const cp_policy* p) {
     if (!h) return fail(h, "cp_set_policy: null handle");
     if (!p) {
@@ -775,7 +794,7 @@ int cp_set_policy(cp_handle* h, const cp_policy* p) {
     h->pol.group = p->group;
     h->pol.floats = floats;
     h->pol_on = true;
-    return 0;
+    return es_scratch(h, "cp_set_policy");
 }
 
 static int policy_kind(const cp_handle* h) {
@@ -793,13 +812,16 @@ int cp_policy_act(cp_handle* h, const float* obs, const float* noise, void* acti
             return fail(h, "cp_policy_act: a caller noise pointer together with in-kernel noise (cp_set_policy_noise); "
                            "pass NULL or turn one of them off");
     }
+    if (h->es.kind != CP_ES_OFF && h->pol.population > 1)
+        return fail(h, "cp_policy_act: ES perturbations (cp_set_policy_es) take cp_policy.weights as one centre [F]; "
+                       "the policy is a population [P][F]");
     hipStream_t st = (hipStream_t)stream;
     CP_TRY(h, hipSetDevice(h->device));
     cpc::Pol pol = h->pol;
     pol.obs_in = obs;
     pol.noise = noise;
     pol.actions_out = actions_out;
-    CP_TRY(h, cp::launch_policy_act(policy_kind(h), h->cfg, h->b, pol, st));
+    CP_TRY(h, cp::launch_policy_act(policy_kind(h), h->cfg, h->b, pol, h->es, st));
     CP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -862,6 +884,75 @@ int cp_policy_noise_set(cp_handle* h, const float* in, void* stream) {
     const size_t bytes = (size_t)h->cfg.num_envs * 4 * sizeof(float);
     if (in) CP_TRY(h, hipMemcpyAsync(h->pol.noise_state, in, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     else CP_TRY(h, hipMemsetAsync(h->pol.noise_state, 0, bytes, (hipStream_t)stream));
+    return 0;
+}
+
+// the checks of a cp_policy_es that need no handle
+static int policy_es_check(cp_handle* h, const cp_policy_es* p, const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (!p) return fail(h, w + "null cp_policy_es");
+    if (p->kind != CP_ES_OFF && p->kind != CP_ES_BYTES4) return fail(h, w + "kind must be CP_ES_OFF or CP_ES_BYTES4");
+    if (p->flags & ~CP_ES_ANTITHETIC) return fail(h, w + "flags holds an unknown CP_ES_* bit");
+    if (!std::isfinite(p->sigma) || p->sigma < 0.0f) return fail(h, w + "sigma must be finite and >= 0");
+    if (p->population < 1) return fail(h, w + "population must be >= 1");
+    if (p->group < 1) return fail(h, w + "group must be >= 1 (consecutive global env ids per member)");
+    return 0;
+}
+
+int cp_policy_es_check(const cp_policy_es* p) { return policy_es_check(nullptr, p, "cp_policy_es_check"); }
+
+int cp_set_policy_es(cp_handle* h, const cp_policy_es* p) {
+    if (!h) return fail(h, "cp_set_policy_es: null handle");
+    if (!p || p->kind == CP_ES_OFF) {
+        h->es.kind = CP_ES_OFF;  // the scratch stays
+        return 0;
+    }
+    if (policy_es_check(h, p, "cp_set_policy_es")) return -1;
+    if (h->f64) return fail(h, "cp_set_policy_es: the MLP policy is fp32 only (not for CP_PRECISION_F64 handles)");
+    if (h->cfg.env_id_offset < 0)
+        return fail(h, "cp_set_policy_es: needs env_id_offset >= 0 (the member is (global id / group) % population)");
+    h->es.kind = p->kind;
+    h->es.flags = p->flags;
+    h->es.sigma = p->sigma;
+    h->es.generation = p->generation;
+    h->es.seed = p->seed;
+    h->es.population = p->population;
+    h->es.group = p->group;
+    if (es_scratch(h, "cp_set_policy_es")) {
+        h->es.kind = CP_ES_OFF;
+        return -1;
+    }
+    return 0;
+}
+
+// what cp_policy_es_weights and cp_policy_es_gradient reject alike
+static int es_range_check(cp_handle* h, int64_t member_lo, int32_t count, const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (h->es.kind == CP_ES_OFF) return fail(h, w + "ES is off (cp_set_policy_es)");
+    if (!h->pol_on) return fail(h, w + "no policy set (cp_set_policy)");
+    if (h->pol.population > 1) return fail(h, w + "the policy is a population [P][F], not one centre [F]");
+    if (member_lo < 0 || count < 1 || member_lo + count > h->es.population)
+        return fail(h, w + "the member range must lie in [0, population) and hold at least one member");
+    return 0;
+}
+
+int cp_policy_es_weights(cp_handle* h, int64_t member_lo, int32_t count, float* out, void* stream) {
+    if (!h || !out) return fail(h, "cp_policy_es_weights: null argument");
+    if (es_range_check(h, member_lo, count, "cp_policy_es_weights")) return -1;
+    CP_TRY(h, hipSetDevice(h->device));
+    cp::launch_policy_es_weights(h->es, h->pol.weights, (int)h->pol.floats, member_lo, count, out, (hipStream_t)stream);
+    CP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+int cp_policy_es_gradient(cp_handle* h, int64_t member_lo, int32_t count, const float* coeff, float* grad_out,
+                          void* stream) {
+    if (!h || !coeff || !grad_out) return fail(h, "cp_policy_es_gradient: null argument");
+    if (es_range_check(h, member_lo, count, "cp_policy_es_gradient")) return -1;
+    CP_TRY(h, hipSetDevice(h->device));
+    cp::launch_policy_es_gradient(h->es, (int)h->pol.floats, member_lo, count, coeff, h->es_partial, grad_out,
+                                  (hipStream_t)stream);
+    CP_TRY(h, hipGetLastError());
     return 0;
 }
 

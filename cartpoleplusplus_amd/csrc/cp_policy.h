@@ -1,7 +1,9 @@
 // cp_policy.h — the in-kernel dense ReLU MLP policy (cp_set_policy): the agents'
 // observation -> small MLP -> action (lrpg_cartpole.py:149-163, ddpg_cartpole.py:121-138), evaluated by
 // one lane per env by cp_policy_act_kernel, or, for a policy population whose members change inside a wave, by
-// one member run per wave (cp_policy_member_kernel, below).  fp32 only; included by cp_env.h inside namespace CP_NS.
+// one member run per wave (cp_policy_member_kernel, below).  With seeded ES perturbations on (cp_set_policy_es) the
+// members are formed from one centre while they are staged (cp_policy_es_kernel, and the weights / gradient kernels
+// at the end).  fp32 only; included by cp_env.h inside namespace CP_NS.
 //
 // The arithmetic order is part of the C-ABI's contract (include/cartpole_amd.h): per unit acc = b[j], then
 // acc = fmaf(W[j][i], x[i], acc) for i ascending; hidden units max(acc, 0) as acc > 0 ? acc : 0.
@@ -346,6 +348,112 @@ CP_DEV void member_block(const float* wrow, float bias, const float* xs, float* 
         *reinterpret_cast<float4*>(out + k) = make_float4(acc[k], acc[k + 1], acc[k + 2], acc[k + 3]);
 }
 
+// ---- seeded ES perturbations (cp_set_policy_es; the arithmetic is spelled out in include/cartpole_amd.h and is
+// part of the contract): member m's weights are theta + s sigma eps(e, f), eps from one Philox word per parameter.
+constexpr float kEsK = 0x1.bb688cp-8f;  // the float32 nearest to 21845^(-1/2)
+struct EsMember {
+    uint64_t e;  // the draw: m >> 1 with ANTITHETIC, else m
+    bool neg;    // s = -1: odd m with ANTITHETIC
+};
+CP_DEV EsMember es_member(const cpc::PolEs& es, uint64_t m) {
+    const bool anti = (es.flags & CP_ES_ANTITHETIC) != 0;
+    return {anti ? m >> 1 : m, anti && (m & 1u)};
+}
+// The four words of Philox block blk: the parameters 4 blk .. 4 blk + 3.  philox4's rounds with each 32 x 32
+// product written as one 64-bit multiply (a single v_mad_u64_u32 instead of a lo / hi pair: the draw is most of
+// what the ES kernels do, and those multiplies are most of the draw); the same words.
+CP_DEV void es_words(const cpc::PolEs& es, uint64_t e, uint32_t blk, uint32_t w[4]) {
+    uint32_t c0 = 0xC0000000u + blk, c1 = es.generation, c2 = (uint32_t)e, c3 = (uint32_t)(e >> 32);
+    uint32_t k0 = (uint32_t)es.seed, k1 = (uint32_t)(es.seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) {
+            k0 += 0x9E3779B9u;
+            k1 += 0xBB67AE85u;
+        }
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0;
+        c1 = (uint32_t)p1;
+        c2 = n2;
+        c3 = (uint32_t)p0;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+CP_DEV float es_epsilon(uint32_t w) {
+    const uint32_t S = __builtin_amdgcn_sad_u8(w, 0u, 0u);  // the sum of the four bytes, one instruction
+    return ((float)S - 510.0f) * kEsK;
+}
+CP_DEV float es_weight(float theta, float eps, float sigma, bool neg) {
+    const float d = sigma * eps;
+    return neg ? theta - d : theta + d;
+}
+
+// The ES form of member_stage_weights: the layer's [W | b] range is the parameters [fbase, fbase + total) of
+// member m, formed from the centre (cache resident, read by dword loads: it may start at any multiple of
+// 4 bytes) and written to the same LDS image.  A lane takes whole Philox blocks, so the first and last block of a
+// layer are partial.  The next block's four centre floats are loaded before this block's draw, from addresses
+// clamped into the layer (loaded and dropped outside it): a load waited for per element was most of the kernel's
+// time.  The LDS position is carried from block to block (a wave-wide trip advances a lane by 256 floats), as in
+// member_stage_weights.
+CP_DEV void es_stage_weights(const cpc::PolEs& es, uint64_t m, const float* theta, int fbase, int nin, int nout,
+                             float* wl, int lane) {
+    const int pad = (nin | 1) - nin, total = nout * nin + nout;
+    const EsMember mem = es_member(es, m);
+    const float* th = theta + fbase;
+    const int blk1 = (fbase + total - 1) >> 2;
+    int blk = (fbase >> 2) + lane;
+    if (blk > blk1) return;
+    auto load = [&](int lf, float x[4]) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int f = lf + k < 0 ? 0 : lf + k;
+            x[k] = th[f < total ? f : total - 1];
+        }
+    };
+    int lf = 4 * blk - fbase;  // the block's first parameter within the layer: -3 .. total - 1
+    // column i and LDS index a = row * stride + i of parameter lf; a block that starts before the layer counts
+    // up to (0, 0) from i = a = lf < 0
+    int i = lf, a = lf;
+    if (lf >= 0) {
+        const int j = lf / nin;
+        i = lf - j * nin;
+        a = lf + j * pad;
+    }
+    const int q = (4 * WAVE) / nin, r = 4 * WAVE - q * nin, qa = 4 * WAVE + q * pad;
+    float x[4];
+    load(lf, x);
+    for (; blk <= blk1; blk += WAVE) {
+        float xn[4];
+        load(lf + 4 * WAVE, xn);
+        uint32_t w[4];
+        es_words(es, mem.e, (uint32_t)blk, w);
+        int ii = i, aa = a;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (lf + k >= 0 && lf + k < total) wl[aa] = es_weight(x[k], es_epsilon(w[k]), es.sigma, mem.neg);
+            ++aa;
+            if (++ii >= nin) {
+                ii = 0;
+                aa += pad;
+            }
+        }
+        lf += 4 * WAVE;
+        i += r;
+        a += qa;
+        while (i < 0) {  // only after a block that started before the layer
+            i += nin;
+            a -= pad;
+        }
+        if (i >= nin) {
+            i -= nin;
+            a += pad;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = xn[k];
+    }
+}
+
 template <int KIND>
 __global__ void __launch_bounds__(WAVE) cp_policy_member_kernel(cp_config cfg, Bufs b, cpc::Pol pol, cps::PolicyRuns runs) {
     extern __shared__ float4 policy_lds[];
@@ -403,3 +511,127 @@ __global__ void __launch_bounds__(WAVE) cp_policy_member_kernel(cp_config cfg, B
     policy_head<KIND>(pol, [&](int j) { return zt[j * ES]; }, pol.noise ? pol.noise + (size_t)row * 4 : nullptr, ldint(CP_SF_STEPS), ldint(CP_SF_EPISODE),
                       (uint64_t)(cfg.env_id_offset + row), pol.actions_out, (size_t)row, a);
 }
+
+// cp_policy_act with ES on, for every G and offset (the lane-per-env kernels read weights by scalar loads and
+// cannot perturb them): cp_policy_member_kernel with the ES struct's P and G and es_stage_weights where that one
+// loads a member's weights.  A copy, not a shared body: the population kernel's device code stays what it was.
+template <int KIND>
+__global__ void __launch_bounds__(WAVE) cp_policy_es_kernel(cp_config cfg, Bufs b, cpc::Pol pol, cpc::PolEs es,
+                                                            cps::PolicyRuns runs) {
+    extern __shared__ float4 policy_lds[];
+    float* const lds = reinterpret_cast<float*>(policy_lds);
+    const int B = cfg.num_envs, lane = threadIdx.x;
+    const cps::PolicyChunk ch = cps::policy_chunk(cfg.env_id_offset, es.group, es.population, B, runs, (int)blockIdx.x);
+    const int n = ch.n, row = ch.lo + lane;
+    if (n <= 0) return;  // a short first or last run's trailing chunk (the whole wave leaves)
+    const bool mine = lane < n;
+    const SoaT<float> st = SoaT<float>::make(b.state, B, CP_STATE_FIELDS);
+    const uint32_t o = SoaT<float>::eoff(mine ? row : ch.lo);
+    auto ldint = [&](int f) { return (int32_t)__float_as_uint(st.ld(f, o)); };
+    const bool live = mine && ldint(CP_SF_DONE) == 0;
+    if (mine && !live) policy_zero_action<KIND>(pol.actions_out, (size_t)row);
+    if (__builtin_amdgcn_ballot_w64(live) == 0) return;  // every env of the chunk is done
+
+    int amax = 0;
+    for (int l = 0; l <= pol.num_layers; ++l) amax = pol.width[l] > amax ? pol.width[l] : amax;
+    const int ES = cps::policy_env_stride(es.group, B), tile = amax * ES;
+    float* const wl = lds + 2 * tile;
+    {   // the chunk's obs rows (contiguous in obs_in) into tile 0, transposed to [unit][env]
+        const int nin = pol.width[0], total = n * nin;
+        const float* obs = pol.obs_in + (size_t)ch.lo * nin;
+        for (int f = lane; f < total; f += WAVE) {
+            const int e = f / nin;
+            lds[(f - e * nin) * ES + e] = obs[f];
+        }
+    }
+    int fbase = 0;  // the layer's first parameter index
+    int half = 0;
+    for (int l = 0; l < pol.num_layers; ++l) {
+        const int nin = pol.width[l], nout = pol.width[l + 1], stride = nin | 1;
+        const bool hidden = l + 1 < pol.num_layers;
+        es_stage_weights(es, (uint64_t)ch.member, pol.weights, fbase, nin, nout, wl, lane);
+        __syncthreads();
+        const float* src = lds + half * tile;
+        float* dst = lds + (half ^ 1) * tile;
+        for (int jb = 0; jb < nout; jb += WAVE) {
+            const bool store = jb + lane < nout;
+            const int j = store ? jb + lane : nout - 1;  // lanes past the last unit repeat it, unstored
+            const int fb = nout * nin + j, jbias = fb / nin;
+            const float bias = wl[jbias * stride + (fb - jbias * nin)];
+            const float* wrow = wl + j * stride;
+            int e0 = 0;
+            for (; e0 + 4 < n; e0 += 16) member_block<16>(wrow, bias, src + e0, dst + j * ES + e0, ES, nin, hidden, store);
+            for (; e0 < n; e0 += 4) member_block<4>(wrow, bias, src + e0, dst + j * ES + e0, ES, nin, hidden, store);
+        }
+        __syncthreads();
+        fbase += nout * nin + nout;
+        half ^= 1;
+    }
+    if (!live) return;
+    const float* zt = lds + half * tile + lane;  // the last layer's tile: unit j of this lane's env
+    float a[4];
+    policy_head<KIND>(pol, [&](int j) { return zt[j * ES]; }, pol.noise ? pol.noise + (size_t)row * 4 : nullptr, ldint(CP_SF_STEPS), ldint(CP_SF_EPISODE),
+                      (uint64_t)(cfg.env_id_offset + row), pol.actions_out, (size_t)row, a);
+}
+
+#ifdef CP_POLICY  // not templates, so every includer would emit them: the fp32 translation unit only
+// cp_policy_es_weights: one thread per (member, Philox block) of the members [lo, lo + count), out [count][F]
+__global__ void __launch_bounds__(256) cp_policy_es_weights_kernel(cpc::PolEs es, const float* theta, int F, int64_t lo,
+                                                                   int count, float* out) {
+    const int nblk = (F + 3) >> 2;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)count * nblk) return;
+    const int mi = (int)(t / nblk), blk = (int)(t - (int64_t)mi * nblk);
+    const EsMember mem = es_member(es, (uint64_t)(lo + mi));
+    uint32_t w[4];
+    es_words(es, mem.e, (uint32_t)blk, w);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int f = 4 * blk + k;
+        if (f < F) out[(size_t)mi * F + f] = es_weight(theta[f], es_epsilon(w[k]), es.sigma, mem.neg);
+    }
+}
+
+// cp_policy_es_gradient, first stage: one thread per (Philox block, member slice) sums its slice's
+// coeff * s * eps in registers, draws ascending, into partial[slice][F].  With ANTITHETIC a draw e serves the
+// members 2e and 2e + 1 with c = c_2e - c_2e+1 (a member outside [lo, lo + count) counts 0).
+__global__ void __launch_bounds__(256) cp_policy_es_gradient_kernel(cpc::PolEs es, int F, int64_t lo, int count,
+                                                                    const float* coeff, float* partial) {
+    const int blk = blockIdx.x * 256 + threadIdx.x;
+    if (4 * blk >= F) return;
+    const bool anti = (es.flags & CP_ES_ANTITHETIC) != 0;
+    const int64_t hi = lo + count;
+    const int64_t e_lo = anti ? lo >> 1 : lo, e_hi = anti ? (hi + 1) >> 1 : hi;  // the draws [e_lo, e_hi)
+    const int64_t per = (e_hi - e_lo + gridDim.y - 1) / gridDim.y;
+    const int64_t a = e_lo + (int64_t)blockIdx.y * per, z = a + per < e_hi ? a + per : e_hi;
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int64_t e = a; e < z; ++e) {
+        float c;
+        if (anti) {
+            const float c0 = 2 * e >= lo ? coeff[2 * e - lo] : 0.0f, c1 = 2 * e + 1 < hi ? coeff[2 * e + 1 - lo] : 0.0f;
+            c = c0 - c1;
+        } else {
+            c = coeff[e - lo];
+        }
+        uint32_t w[4];
+        es_words(es, (uint64_t)e, (uint32_t)blk, w);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float t = c * es_epsilon(w[k]);
+            acc[k] = acc[k] + t;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (4 * blk + k < F) partial[(size_t)blockIdx.y * F + 4 * blk + k] = acc[k];
+}
+
+// second stage: the slices' partial sums in slice order (no atomics: equal calls give equal bits)
+__global__ void __launch_bounds__(256) cp_policy_es_reduce_kernel(int F, int slices, const float* partial, float* grad) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+    float g = partial[f];
+    for (int s = 1; s < slices; ++s) g = g + partial[(size_t)s * F + f];
+    grad[f] = g;
+}
+#endif  // CP_POLICY

@@ -25,6 +25,7 @@ EXPORTS = (
     "cp_nonfinite_counts", "cp_render_kernel_name",
     "cp_policy_floats", "cp_set_policy", "cp_policy_act",
     "cp_policy_noise_check", "cp_set_policy_noise", "cp_policy_noise_get", "cp_policy_noise_set",
+    "cp_policy_es_check", "cp_set_policy_es", "cp_policy_es_weights", "cp_policy_es_gradient",
 )
 
 _lib = None
@@ -91,6 +92,10 @@ def load():
         "cp_set_policy_noise": (I, [VP, P(abi.cp_policy_noise)]),
         "cp_policy_noise_get": (I, [VP, VP, VP]),
         "cp_policy_noise_set": (I, [VP, VP, VP]),
+        "cp_policy_es_check": (I, [P(abi.cp_policy_es)]),
+        "cp_set_policy_es": (I, [VP, P(abi.cp_policy_es)]),
+        "cp_policy_es_weights": (I, [VP, C.c_int64, C.c_int32, VP, VP]),
+        "cp_policy_es_gradient": (I, [VP, C.c_int64, C.c_int32, VP, VP, VP]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

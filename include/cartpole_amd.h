@@ -388,6 +388,62 @@ int cp_set_policy_noise(cp_handle* h, const cp_policy_noise* p);
 int cp_policy_noise_get(cp_handle* h, float* out, void* stream);
 int cp_policy_noise_set(cp_handle* h, const float* in, void* stream);
 
+/* ---- Seeded ES perturbations: a policy population that is a function of one centre, a seed and the member ----
+ * Evolution strategies evaluate P members W'_m = theta + sigma * eps_m and update theta by sum_m c_m eps_m.
+ * With ES on, cp_policy.weights is the centre theta, [F], one weight set (cp_policy.population must be <= 1:
+ * cp_policy_act rejects a [P][F] policy while ES is on), and cp_policy_act's kernel forms member m's weights
+ * while it stages them, from theta, the seed and m; nothing [P][F] exists and no eps is kept.  Env i reads member
+ * m = ((env_id_offset + i) / group) % population (64-bit arithmetic) of the ES struct's fields: the populations'
+ * rule, with the same invariance under sharding.  ABI 8, additive: no existing struct or signature changes.
+ *
+ * Arithmetic (all fp32, every product and sum rounded on its own; part of the contract).  f is the parameter's
+ * index in the packed order, 0 .. F-1:
+ *   1. e = m >> 1 and s = -1 for odd m with CP_ES_ANTITHETIC; otherwise e = m and s = +1.
+ *   2. (w0..w3) = Philox4x32-10(ctr = (0xC0000000 + (f >> 2), generation, e_lo, e_hi), key = seed).
+ *   3. w = w[f & 3]; S = the sum of w's four bytes, 0 .. 1020.
+ *   4. eps = ((float)S - 510.0f) * K, K = 0x1.bb688cp-8f, the float32 nearest to 21845^(-1/2).  The
+ *      subtraction is exact and the product rounds once.  A byte is uniform with variance (256^2 - 1) / 12, so
+ *      S has mean 510 and variance 21845: eps is symmetric with unit variance, |eps| <= 3.451 (excess
+ *      kurtosis -0.3).
+ *   5. d = sigma * eps.
+ *   6. W'[f] = theta[f] + d for s = +1, theta[f] - d for s = -1.
+ * The layers and heads then run on W' as above (acc = b'[j], fmaf with i ascending).  Exploration noise and
+ * all four heads work unchanged with ES on. */
+#define CP_ES_OFF    0
+#define CP_ES_BYTES4 1            /* the eps above */
+#define CP_ES_ANTITHETIC 0x1      /* members 2k and 2k+1 share eps with signs + and - */
+typedef struct cp_policy_es {
+    int32_t kind, flags;
+    float   sigma;
+    uint32_t generation;          /* the caller bumps it once per ES iteration */
+    uint64_t seed;                /* Philox key, independent of cp_policy.seed and the noise seed */
+    int32_t population;           /* P >= 1 perturbed members */
+    int32_t group;                /* G >= 1 consecutive global env ids per member */
+} cp_policy_es;
+
+/* The checks that need no handle: an unknown kind, unknown flag bits, sigma not finite or below 0,
+ * population < 1, group < 1.  0 if valid; < 0 and the cause in cp_last_error(NULL) otherwise.  No GPU. */
+int cp_policy_es_check(const cp_policy_es* p);
+
+/* Turn ES on (a copy of *p) or off (NULL, or kind CP_ES_OFF).  Rejected: fp64 handles, a negative
+ * env_id_offset and whatever cp_policy_es_check rejects.  Independent of cp_set_policy: either may be called
+ * first.  The first call that turns ES on allocates cp_policy_es_gradient's scratch (freed by cp_destroy).
+ * cp_step and cp_rollout are unaffected. */
+int cp_set_policy_es(cp_handle* h, const cp_policy_es* p);
+
+/* W' of the members [member_lo, member_lo + count) into out [count][F] (device), by the device function
+ * cp_policy_act's kernel stages with: a member's checkpoint.  Rejected: ES off, no policy set, a [P][F] policy,
+ * a member range outside [0, P) or empty. */
+int cp_policy_es_weights(cp_handle* h, int64_t member_lo, int32_t count, float* out, void* stream);
+
+/* grad_out[f] = sum over m in [member_lo, member_lo + count) of coeff[m - member_lo] * s(m) * eps(e(m), f), fp32,
+ * coeff [count] and grad_out [F] on the device; the caller scales by lr / (P sigma).  With CP_ES_ANTITHETIC a
+ * pair's eps is drawn once for (c_2k - c_2k+1).  No float atomics: the summation order is fixed, so equal calls
+ * give equal bits.  A rank passes its own member range and all-reduces grad_out.  Rejections as
+ * cp_policy_es_weights. */
+int cp_policy_es_gradient(cp_handle* h, int64_t member_lo, int32_t count, const float* coeff, float* grad_out,
+                          void* stream);
+
 /* Optional per-substep 12-state readback of both poles (bullet_cartpole.py:212-234,
  * exposed there as monkey_positions / monkey_velocities):
  * float32 [B][2 poles][R][S][4][3] = (xyz, rpy, linvel, angvel).  Enabled when

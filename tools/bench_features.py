@@ -25,7 +25,9 @@ with the same code (the P = 1 gate: run the two alternately in one session).  --
     off     cp_policy_act alone, noise off (nothing newer than set_policy / policy_act, so `--tree OTHER_CHECKOUT
             --noise off` times the parent build: the noise-off gate, the two builds alternating in one session)
     kernel  K x (policy_act with in-kernel OU + step)
-    torch   K x (the caller's torch OU update of INTEGRATION.md + policy_act(noise=x) + step)"""
+    torch   K x (the caller's torch OU update of INTEGRATION.md + policy_act(noise=x) + step)
+
+--policy --es [LEGS]: the seeded ES perturbation legs (DESIGN.md §9.5 "ES perturbations"; es_bench below)."""
 import argparse
 import json
 import os
@@ -158,6 +160,108 @@ def population_bench(args):
             f.write(line + "\n")
 
 
+ES_LEGS = {"anti": (None, 1, True), "plain": (None, 1, False), "g8": (8192, 8, True)}   # (P, G, antithetic); None: B
+
+
+def es_bench(args):
+    """--policy --es [LEGS]: seeded ES perturbations (DESIGN.md §9.5 "ES perturbations"), the population legs' net,
+    head and sizes.  anti / plain / g8: cp_policy_act alone and the closed loop with ES on; d: the materialised
+    [P][F] population of the same members (P = B, G = 1: the population legs' leg (d)) as the yardstick; grad:
+    policy_es_gradient at P = B against the einsum over kept noise tensors."""
+    import statistics
+    B, K, R = args.batch, args.steps, 3
+    dev = torch.device("cuda", 0)
+    widths = (14 * R, 100, 50, 10)
+    F = sum(o * (i + 1) for i, o in zip(widths[:-1], widths[1:]))
+    sigma = 0.05
+    env = BatchedCartpole(B, 0, action_repeats=R, initial_force=55.0, autoreset=True, seed=1234)
+    env.reset()
+    g = torch.Generator(device=dev).manual_seed(1234)
+    layers = [(torch.randn((o, i), device=dev, generator=g) / i ** 0.5, torch.randn((o,), device=dev, generator=g) * 0.1)
+              for i, o in zip(widths[:-1], widths[1:])]
+
+    def run(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    def series(fn):
+        run(fn)  # warm-up
+        ms = [run(fn) for _ in range(args.repeats)]
+        med = statistics.median(ms)
+        return {"ms": ms, "median_ms": med, "spread": (max(ms) - min(ms)) / med}
+
+    def act_and_loop(res):
+        res["act"] = series(lambda: [env.policy_act() for _ in range(K)])
+        res["act_us_per_launch"] = res["act"]["median_ms"] * 1e3 / K
+        env.reset()
+        res["act_step_loop"] = series(lambda: [env.step(env.policy_act()) for _ in range(K)])
+        res["act_step_loop_env_steps_per_s"] = B * K / (res["act_step_loop"]["median_ms"] * 1e-3)
+
+    out = {"tree": os.path.abspath(_TREE), "batch": B, "steps": K, "repeats": args.repeats,
+           "policy": "42-100-50-10 sample", "floats_per_member": F, "sigma": sigma, "legs": {}}
+    for leg in args.es.split(","):
+        if leg in ES_LEGS:
+            P, G, anti = ES_LEGS[leg]
+            P = B if P is None else P
+            env.set_policy(layers, "sample", epsilon=0.05, seed=7)
+            env.set_policy_es(P, sigma, group=G, seed=11, antithetic=anti)
+            # the centre, and the gradient's slices (64 x F floats, the library's) : all the ES path holds
+            res = {"population": P, "group": G, "antithetic": anti, "device_bytes": F * 4 + 64 * F * 4}
+            act_and_loop(res)
+        elif leg == "d":
+            env.set_policy(layers, "sample", epsilon=0.05, seed=7)
+            env.set_policy_es(B, sigma, group=1, seed=11)
+            W = env.policy_es_weights()
+            env.set_policy_es(None)
+            env.set_policy(_stacked(W, widths), "sample", epsilon=0.05, seed=7, group=1)
+            del W
+            # the [P][F] weights, and the [P][F] noise the caller keeps for the update
+            res = {"population": B, "group": 1, "device_bytes": 2 * B * F * 4}
+            act_and_loop(res)
+        elif leg == "grad":
+            env.set_policy(layers, "sample", epsilon=0.05, seed=7)
+            env.set_policy_es(B, sigma, group=1, seed=11)
+            fit = torch.randn((B,), device=dev, generator=g)
+            res = {"population": B, "es_gradient": series(lambda: [env.policy_es_gradient(fit) for _ in range(10)])}
+            res["es_gradient_us"] = res["es_gradient"]["median_ms"] * 1e3 / 10
+            noise = [(torch.randn((B, o, i), device=dev, generator=g), torch.randn((B, o), device=dev, generator=g))
+                     for i, o in zip(widths[:-1], widths[1:])]
+            res["einsum"] = series(lambda: [[(torch.einsum("b,boi->oi", fit, nw), torch.einsum("b,bo->o", fit, nb))
+                                             for nw, nb in noise] for _ in range(10)])
+            res["einsum_us"] = res["einsum"]["median_ms"] * 1e3 / 10
+            res["einsum_noise_bytes"] = B * F * 4
+            del noise
+        else:
+            raise SystemExit(f"--es: unknown leg {leg!r} (anti, plain, g8, d, grad)")
+        env.set_policy_es(None)
+        env.set_policy(None)
+        torch.cuda.empty_cache()
+        out["legs"][leg] = res
+    if "d" in out["legs"]:
+        for leg, res in out["legs"].items():
+            if "act_us_per_launch" in res:
+                res["act_over_leg_d"] = res["act_us_per_launch"] / out["legs"]["d"]["act_us_per_launch"]
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def _stacked(W, widths):
+    """Packed rows (P, F) as a stacked population [(W (P, out, in), b (P, out)), ...]."""
+    out, o = [], 0
+    for i, n in zip(widths[:-1], widths[1:]):
+        out.append((W[:, o:o + n * i].reshape(-1, n, i), W[:, o + n * i:o + n * i + n]))
+        o += n * i + n
+    return out
+
+
 NOISE_SIZES = ((4096, 2), (65536, 3))   # (B, R): C2, and the full-size batch of the other policy legs
 
 
@@ -237,6 +341,8 @@ def main():
     ap.add_argument("--noise", nargs="?", const="off,kernel,torch", default=None,
                     help="with --policy: the exploration-noise legs (off, kernel, torch)")
     ap.add_argument("--population", nargs="?", const="a,b,c,d,e", default=None, help="with --policy: the population legs")
+    ap.add_argument("--es", nargs="?", const="d,anti,plain,g8,grad", default=None,
+                    help="with --policy: the ES perturbation legs (d, anti, plain, g8, grad)")
     ap.add_argument("--tree", default=None, help="import cartpoleplusplus_amd from this checkout instead of the tool's own")
     ap.add_argument("--copy-tbps", type=float, default=6.29, help="measured copy bandwidth for the weight-streaming floor")
     ap.add_argument("--out", default=None)
@@ -246,6 +352,8 @@ def main():
     ap.add_argument("--ring", type=int, default=1 << 22)
     ap.add_argument("--sample", type=int, default=65536)
     args = ap.parse_args()
+    if args.policy and args.es:
+        return es_bench(args)
     if args.policy and args.population:
         return population_bench(args)
     if args.policy and args.noise:
