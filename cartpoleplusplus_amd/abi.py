@@ -265,6 +265,31 @@ class cp_replay_batch(C.Structure):
                                           "state_1_idx", "state_2_idx")]
 
 
+# ---- returns and advantages of a rollout window (include/cartpole_amd.h: cp_returns)
+CP_RET_EPISODE_TOTAL, CP_RET_DISCOUNTED, CP_RET_GAE = range(3)
+CP_RET_BOUNDARY_SAME_STEP, CP_RET_BOUNDARY_STICKY, CP_RET_BOUNDARY_NEXT_STEP = range(3)
+CP_RET_MASK_OPEN = 0x1
+CP_RET_STANDARDISE = 0x2
+RET_KINDS = {"episode_total": CP_RET_EPISODE_TOTAL, "discounted": CP_RET_DISCOUNTED, "gae": CP_RET_GAE}
+RET_BOUNDARIES = {"same_step": CP_RET_BOUNDARY_SAME_STEP, "sticky": CP_RET_BOUNDARY_STICKY,
+                  "next_step": CP_RET_BOUNDARY_NEXT_STEP}
+
+
+class cp_returns(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("boundary", C.c_int32),
+        ("flags", C.c_uint32),
+        ("gamma", C.c_float),
+        ("lam", C.c_float),          # `lambda` in the header
+        ("steps", C.c_int32),
+        ("num_envs", C.c_int32),
+        ("env_id_offset", C.c_int64),
+        ("population", C.c_int32),
+        ("group", C.c_int32),
+    ]
+
+
 def state_ints(values):
     """Integer state fields (steps, episode, done, warm-start ids) from a state array:
     float32 holds the int32 bits; a float64 state (fp64 build) holds them in the first 4

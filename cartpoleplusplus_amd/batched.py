@@ -442,6 +442,26 @@ class BatchedCartpole:
                      "cp_episode_returns")
         return r, n
 
+    def advantages(self, reward, done, kind="episode_total", **kw):
+        """returns.advantages() of a window of this env's (K, B) reward / done tensors (K step() calls or one
+        rollout()), with what the handle knows filled in: `boundary` from the autoreset mode ("sticky" without
+        autoreset), `env_id_offset`, and population / group of the ES setting when ES is on, of the policy
+        population otherwise.  Any of them can still be passed explicitly."""
+        from . import returns
+        boundary = {abi.CP_AUTORESET_OFF: "sticky", abi.CP_AUTORESET_SAME_STEP: "same_step",
+                    abi.CP_AUTORESET_NEXT_STEP: "next_step"}[self.cfg.autoreset]
+        population, group = 1, 1
+        if self.policy_es is not None:
+            population, group = self.policy_es.population, self.policy_es.group
+        elif self.policy is not None and self.policy.population > 1:
+            population, group = self.policy.population, self.policy.group
+        kw.setdefault("boundary", boundary)
+        kw.setdefault("env_id_offset", self.cfg.env_id_offset)
+        kw.setdefault("population", population)
+        kw.setdefault("group", group)
+        kw.setdefault("stream", self._stream().value or 0)
+        return returns.advantages(reward, done, kind, **kw)
+
     def timing_begin(self, max_launches):
         """Record HIP events around every step / reset kernel launch (see cp_timing_begin)."""
         native.check(self.h, self.lib.cp_timing_begin(self.h, int(max_launches)), "cp_timing_begin")

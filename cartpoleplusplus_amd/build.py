@@ -19,7 +19,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # kernels + raster / event / replay kernels + the C-ABI, and the fp64 env kernels
 SRCS = [os.path.join(HERE, "csrc", f) for f in ("cp_kernels.hip", "cp_kernels64.hip")]
 DEPS = SRCS + [os.path.join(HERE, "csrc", f) for f in ("cp_common.h", "cp_shapes.h", "cp_env.h", "cp_physics.h",
-                                                     "cp_math.h", "cp_raster.h", "cp_replay.h", "cp_policy.h")] + [
+                                                     "cp_math.h", "cp_raster.h", "cp_replay.h", "cp_returns.h",
+                                                     "cp_policy.h")] + [
     os.path.join(HERE, "..", "include", "cartpole_amd.h")]
 LIB = os.path.join(HERE, "libcartpole_hip.so")
 STAMPS_LIB = os.path.join(HERE, "libcartpole_hip_stamps.so")

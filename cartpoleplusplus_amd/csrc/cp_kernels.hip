@@ -7,7 +7,7 @@
 // over `real` and instantiated here for fp32 (namespace cp, the product path) and in
 // cp_kernels64.hip for fp64 (namespace cp64, the parity variant, cp_config.precision).
 // This file also holds the fp32-only kernels (reset-mask compaction, raster obs, event
-// log records, replay memory) and every C-ABI entry point (include/cartpole_amd.h).
+// log records, replay memory, returns and advantages) and every C-ABI entry point (include/cartpole_amd.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +36,7 @@
 
 #include "cp_raster.h"
 #include "cp_replay.h"
+#include "cp_returns.h"
 
 namespace cp {
 
@@ -1382,6 +1383,76 @@ int cp_replay_sample(const cp_replay* rm, int n, const int32_t* idxs, uint64_t s
         case 2: hipLaunchKernelGGL(cprm::sample_kernel<2>, grid, dim3(256), 0, st, *rm, n, idxs, k0, k1, c1, c2, *out); break;
         default: hipLaunchKernelGGL(cprm::sample_kernel<1>, grid, dim3(256), 0, st, *rm, n, idxs, k0, k1, c1, c2, *out);
     }
+    CP_TRY(nullptr, hipGetLastError());
+    return 0;
+}
+
+/* ---- returns and advantages (cp_returns.h) ---- */
+static int returns_check(const cp_returns* p, const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (!p) return fail(nullptr, w + "null cp_returns");
+    if (p->kind != CP_RET_EPISODE_TOTAL && p->kind != CP_RET_DISCOUNTED && p->kind != CP_RET_GAE)
+        return fail(nullptr, w + "kind must be CP_RET_EPISODE_TOTAL, _DISCOUNTED or _GAE");
+    if (p->boundary != CP_RET_BOUNDARY_SAME_STEP && p->boundary != CP_RET_BOUNDARY_STICKY &&
+        p->boundary != CP_RET_BOUNDARY_NEXT_STEP)
+        return fail(nullptr, w + "boundary must be CP_RET_BOUNDARY_SAME_STEP, _STICKY or _NEXT_STEP");
+    if (p->flags & ~(CP_RET_MASK_OPEN | CP_RET_STANDARDISE)) return fail(nullptr, w + "flags holds an unknown CP_RET_* bit");
+    if (p->steps < 1) return fail(nullptr, w + "steps must be >= 1");
+    if (p->num_envs < 1) return fail(nullptr, w + "num_envs must be >= 1");
+    if (!std::isfinite(p->gamma) || p->gamma < 0.0f || p->gamma > 1.0f)
+        return fail(nullptr, w + "gamma must be finite and in [0, 1]");
+    if (!std::isfinite(p->lambda) || p->lambda < 0.0f || p->lambda > 1.0f)
+        return fail(nullptr, w + "lambda must be finite and in [0, 1]");
+    if (p->population < 0) return fail(nullptr, w + "population must be >= 0");
+    if (p->population > 1 && p->group < 1)
+        return fail(nullptr, w + "group must be >= 1 (consecutive global env ids per member)");
+    if (p->env_id_offset < 0 || p->env_id_offset >= ((int64_t)1 << 62))
+        return fail(nullptr, w + "needs 0 <= env_id_offset < 2^62 (the member is (global id / group) % population)");
+    return 0;
+}
+
+int cp_returns_check(const cp_returns* p) { return returns_check(p, "cp_returns_check"); }
+
+int64_t cp_returns_scratch_bytes(const cp_returns* p) {
+    if (returns_check(p, "cp_returns_scratch_bytes")) return -1;
+    return cpret::layout(*p).bytes;
+}
+
+int cp_returns_compute(const cp_returns* p, const float* reward, const uint8_t* done, const float* values,
+                       const float* head, const uint8_t* done_in, const float* tail, float* adv_out,
+                       uint8_t* valid_out, float* carry_out, float* ret_out, double* stats_out, void* scratch,
+                       void* stream) {
+    if (returns_check(p, "cp_returns_compute")) return -1;
+    if (!reward || !done || !adv_out || !valid_out || !scratch)
+        return fail(nullptr, "cp_returns_compute: null reward, done, adv_out, valid_out or scratch");
+    if (p->kind == CP_RET_GAE && !values) return fail(nullptr, "cp_returns_compute: CP_RET_GAE needs values [K+1][B]");
+    if (p->kind != CP_RET_GAE && ret_out) return fail(nullptr, "cp_returns_compute: ret_out is CP_RET_GAE's output");
+    if ((uintptr_t)scratch & 15) return fail(nullptr, "cp_returns_compute: scratch must be 16-byte aligned");
+    const cpret::Layout l = cpret::layout(*p);
+    const int64_t P = p->population > 1 ? p->population : 1;
+    if ((p->flags & CP_RET_STANDARDISE) && P * l.S > 0x7fffffffll)
+        return fail(nullptr, "cp_returns_compute: population too large for one launch");
+    cpret::Args a{};
+    a.K = p->steps;
+    a.B = p->num_envs;
+    a.flags = p->flags;
+    a.gamma = p->gamma;
+    a.c = p->gamma * p->lambda;
+    a.off = p->env_id_offset;
+    a.P = (int32_t)P;
+    a.G = p->population > 1 ? p->group : 1;
+    a.reward = reward;
+    a.done = done;
+    a.values = values;
+    a.head = head;
+    a.done_in = done_in;
+    a.tail = tail;
+    a.adv = adv_out;
+    a.valid = valid_out;
+    a.carry = carry_out;
+    a.ret = ret_out;
+    a.stats = (p->flags & CP_RET_STANDARDISE) ? stats_out : nullptr;
+    cpret::launch(*p, a, scratch, (hipStream_t)stream);
     CP_TRY(nullptr, hipGetLastError());
     return 0;
 }

@@ -26,6 +26,7 @@ EXPORTS = (
     "cp_policy_floats", "cp_set_policy", "cp_policy_act",
     "cp_policy_noise_check", "cp_set_policy_noise", "cp_policy_noise_get", "cp_policy_noise_set",
     "cp_policy_es_check", "cp_set_policy_es", "cp_policy_es_weights", "cp_policy_es_gradient",
+    "cp_returns_check", "cp_returns_scratch_bytes", "cp_returns_compute",
 )
 
 _lib = None
@@ -96,6 +97,9 @@ def load():
         "cp_set_policy_es": (I, [VP, P(abi.cp_policy_es)]),
         "cp_policy_es_weights": (I, [VP, C.c_int64, C.c_int32, VP, VP]),
         "cp_policy_es_gradient": (I, [VP, C.c_int64, C.c_int32, VP, VP, VP]),
+        "cp_returns_check": (I, [P(abi.cp_returns)]),
+        "cp_returns_scratch_bytes": (C.c_int64, [P(abi.cp_returns)]),
+        "cp_returns_compute": (I, [P(abi.cp_returns)] + [VP] * 13),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -709,6 +709,93 @@ typedef struct cp_replay_batch {
 int cp_replay_sample(const cp_replay* rm, int n, const int32_t* idxs, uint64_t seed, uint64_t counter,
                      const cp_replay_batch* out, void* stream);
 
+/* ---- Episode returns, GAE and standardised advantages of a rollout window (lrpg_cartpole.py:200-216,
+ * util.py:37-43) --------------------------------------------------------------------
+ * The on-policy agent's learning signal from the [K][B] reward and done arrays of K cp_step calls or one
+ * cp_rollout: lrpg's episode totals, discounted reward-to-go or GAE(gamma, lambda), optionally standardised
+ * per population member.  Stateless like cp_replay_*: no handle, contiguous caller-owned device arrays, kernels
+ * on `stream`, no allocation and no host synchronisation.  ABI 8, additive: no existing struct or signature
+ * changes.  No floating-point atomics anywhere: two equal calls give equal bits, and the raw outputs (everything
+ * but the standardised adv and stats_out) of an env depend on that env's column only, so they are the same
+ * however a batch is sharded.
+ *
+ * Sample (k, i) is step k of env i, k = 0 .. K-1, i = 0 .. B-1; reward [K][B] f32, done [K][B] u8 (0 / not 0).
+ *
+ * Padding.  boundary says which samples are not steps of any episode:
+ *   SAME_STEP  none (autoreset in the step that ends the episode: sample k+1 is the next episode's first step).
+ *   STICKY     (k, i) is padding if done_in[i] is set or any done[j][i] with j < k is set (no autoreset: after
+ *              an env's first done every later sample is cp_step's "already done" answer).
+ *   NEXT_STEP  (k, i) is padding if done[k-1][i] is set, or done_in[i] when k = 0 (the sample after a done
+ *              sample is the reset step: reward 0, done 0, the action ignored).
+ * done_in [B] u8 (NULL: all 0) is the done row that preceded the window.  A padding sample gets adv 0,
+ * valid 0 (and ret 0), belongs to no episode, and its own reward and done value are otherwise ignored.
+ *
+ * Segments.  Within an env's column a segment runs from the first non-padding sample after a done sample,
+ * after a padding sample or at k = 0 up to and including the next done sample (a closed segment), or up to
+ * k = K-1 when no done sample follows (the open segment).  Every non-padding sample is in exactly one segment.
+ *
+ * Every invalid sample (valid 0) has adv 0 and ret 0.  All arithmetic below is fp32 with every product and
+ * sum rounded on its own (the library is built with -ffp-contract=off); the order is part of the contract.
+ *
+ * EPISODE_TOTAL (lrpg: batch_advantages += [sum(rewards)] * len(rewards)).  Per segment T starts as head[i]
+ *   if the segment contains k = 0 and head is not NULL, as 0.0f otherwise; then T = T + reward[k][i] for the
+ *   segment's samples in ascending k: the order of sum(rewards) and of the handle's own accumulator, so a
+ *   closed segment's T is cp_episode_returns' value bit for bit.  Every sample of a closed segment gets
+ *   adv T, valid 1.  The open segment is always invalid.  carry_out[i] (may be NULL) is the open segment's
+ *   T, or 0 when the column has no open segment: it is the next window's head.  tail is ignored.
+ * DISCOUNTED (reward-to-go).  G_k = r_k at a done sample, otherwise G_k = r_k + fl(gamma * G_{k+1}), with
+ *   G_K = tail[i] (0 when tail is NULL); adv = G_k.  head is ignored; carry_out, if given, is set to 0.
+ * GAE (values [K+1][B], row K the value after the window).  c = fl(gamma * lambda), formed once.  At a done
+ *   sample A_k = r_k - V_k; otherwise A_k = ((r_k + fl(gamma * V_{k+1})) - V_k) + fl(c * A_{k+1}), with
+ *   A_K = 0; adv = A_k, and ret_out (may be NULL) = A_k + V_k.  head and tail are ignored; carry_out, if
+ *   given, is set to 0.
+ * Both recurrences start afresh below a padding sample (the sample before one is a done sample).  Samples of
+ * the open segment are valid for DISCOUNTED and GAE unless CP_RET_MASK_OPEN is set (EPISODE_TOTAL ignores
+ * the flag).
+ *
+ * CP_RET_STANDARDISE (util.standardise).  Env i belongs to member m = ((env_id_offset + i) / group) %
+ * population (64-bit arithmetic, the populations' rule; population 0 or 1: one member, group unread).  Per
+ * member, over the valid samples of this call's envs that map to it, in fp64: n, mean = sum(x) / n,
+ * std = sqrt(sum((x - mean)^2) / n), and every valid sample's adv becomes (float)((x - mean) / std).  With
+ * n = 0 or std = 0 (lrpg's "converged?" case, :213-216) the member is degenerate: its adv are all 0.  ret_out
+ * is never standardised.  The fp64 sums run in a fixed order that depends on (B, K, population, group,
+ * env_id_offset) only.  stats_out (may be NULL; written only with CP_RET_STANDARDISE) is [P][4] fp64, P =
+ * max(population, 1): n, mean, std, degenerate (0 / 1) per member (a member with no valid sample: 0, 0, 0, 1),
+ * so that a sharded caller can pool its ranks' statistics; the library standardises with this call's only.
+ *
+ * cp_returns_check rejects (cause in cp_last_error(NULL)): an unknown kind, boundary or flag bit; steps < 1 or
+ * num_envs < 1; gamma or lambda not finite or outside [0, 1]; population < 0; group < 1 when population > 1;
+ * env_id_offset < 0 or >= 2^62.  cp_returns_scratch_bytes is the size of `scratch` for *p (> 0; < 0 when *p
+ * is invalid).  cp_returns_compute rejects what the check rejects, a NULL reward, done, adv_out, valid_out or
+ * scratch, GAE without values, and ret_out without GAE.  scratch must be 16-byte aligned; its contents are
+ * scratch only (nothing is kept between calls).  adv_out may not alias reward or values. */
+#define CP_RET_EPISODE_TOTAL 0   /* lrpg: every step gets its episode's total reward */
+#define CP_RET_DISCOUNTED    1   /* reward-to-go, gamma */
+#define CP_RET_GAE           2   /* GAE(gamma, lambda) on values [K+1][B] */
+#define CP_RET_BOUNDARY_SAME_STEP 0   /* a done sample is followed by the next episode's first step */
+#define CP_RET_BOUNDARY_STICKY    1   /* no autoreset: every sample after an env's first done is padding */
+#define CP_RET_BOUNDARY_NEXT_STEP 2   /* the sample after a done sample is the reset step: padding */
+#define CP_RET_MASK_OPEN    1u   /* DISCOUNTED / GAE: samples of an episode still open at the window's end are invalid */
+#define CP_RET_STANDARDISE  2u
+typedef struct cp_returns {
+    int32_t kind, boundary;
+    uint32_t flags;
+    float gamma, lambda;
+    int32_t steps;               /* K */
+    int32_t num_envs;            /* B */
+    int64_t env_id_offset;       /* global id of env 0 */
+    int32_t population;          /* P: 0 or 1 = one member */
+    int32_t group;               /* G: consecutive global env ids per member; read only when population > 1 */
+} cp_returns;
+int     cp_returns_check(const cp_returns* p);            /* no GPU */
+int64_t cp_returns_scratch_bytes(const cp_returns* p);    /* no GPU */
+int     cp_returns_compute(const cp_returns* p, const float* reward, const uint8_t* done,
+                           const float* values /* GAE: [K+1][B] */, const float* head /* [B] | NULL */,
+                           const uint8_t* done_in /* [B] | NULL */, const float* tail /* [B] | NULL */,
+                           float* adv_out /* [K][B] */, uint8_t* valid_out /* [K][B] */,
+                           float* carry_out /* [B] | NULL */, float* ret_out /* GAE: [K][B] | NULL */,
+                           double* stats_out /* [P][4] | NULL */, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,9 @@ with the same code (the P = 1 gate: run the two alternately in one session).  --
     kernel  K x (policy_act with in-kernel OU + step)
     torch   K x (the caller's torch OU update of INTEGRATION.md + policy_act(noise=x) + step)
 
---policy --es [LEGS]: the seeded ES perturbation legs (DESIGN.md §9.5 "ES perturbations"; es_bench below)."""
+--policy --es [LEGS]: the seeded ES perturbation legs (DESIGN.md §9.5 "ES perturbations"; es_bench below).
+
+--returns: returns and advantages of a rollout window (DESIGN.md §9.5 "Returns and advantages"; returns_bench below)."""
 import argparse
 import json
 import os
@@ -253,6 +255,126 @@ def es_bench(args):
             f.write(line + "\n")
 
 
+def _torch_advantages(reward, done, kind, gamma, lam, values, member, P):
+    """What a user writes without the library call (SAME_STEP boundary): loops over k of elementwise ops (forwards
+    for the episode totals, then backwards), and scatter_add for the per-member statistics in float64."""
+    K, B = reward.shape
+    d = done != 0
+    adv = torch.zeros_like(reward)
+    valid = torch.zeros_like(done)
+    ret = None
+    if kind == "episode_total":
+        closing = torch.zeros_like(reward)
+        T = torch.zeros_like(reward[0])
+        for k in range(K):
+            T = T + reward[k]
+            closing[k] = T
+            T = torch.where(d[k], torch.zeros_like(T), T)
+        cur = torch.zeros_like(reward[0])
+        closed = torch.zeros_like(d[0])
+        for k in range(K - 1, -1, -1):
+            closed = closed | d[k]
+            cur = torch.where(d[k], closing[k], cur)
+            adv[k] = torch.where(closed, cur, torch.zeros_like(cur))
+            valid[k] = closed
+    else:
+        c = (torch.tensor(gamma, dtype=torch.float32) * torch.tensor(lam, dtype=torch.float32)).item()
+        A = torch.zeros_like(reward[0])
+        ret = torch.empty_like(reward)
+        for k in range(K - 1, -1, -1):
+            delta = (reward[k] + gamma * values[k + 1]) - values[k]
+            A = torch.where(d[k], reward[k] - values[k], delta + c * A)
+            adv[k] = A
+            ret[k] = A + values[k]
+        valid.fill_(1)
+        return adv, valid, ret
+    x = adv.double()
+    v = (valid != 0).double()
+    idx = member.expand(K, B).reshape(-1)
+    n = torch.zeros(P, dtype=torch.float64, device=reward.device).scatter_add_(0, idx, v.reshape(-1))
+    s1 = torch.zeros_like(n).scatter_add_(0, idx, (x * v).reshape(-1))
+    mean = s1 / n.clamp(min=1)
+    dev = (x - mean[member]) * v
+    s2 = torch.zeros_like(n).scatter_add_(0, idx, (dev * dev).reshape(-1))
+    std = (s2 / n.clamp(min=1)).sqrt()
+    ok = (n > 0) & (std > 0)
+    out = torch.where(ok[member], dev / std.clamp(min=1e-300)[member], torch.zeros_like(dev)).float()
+    return out, valid, ret
+
+
+def returns_bench(args):
+    """--returns: cp_returns_compute (cartpoleplusplus_amd.returns.advantages) against the torch loop above, in one
+    process on one build: K = --steps, at B = 65,536 with P = 1 and at B = 4,096 with P = 16, G = 256; the legs
+    EPISODE_TOTAL + STANDARDISE and GAE.  us per call: one warm-up run and the median of --repeats runs (a run is
+    `calls` back-to-back calls between two events), spread = max - min over the median.  Bytes per sample, the
+    algorithm's: reward, done, adv, valid = 10; GAE adds values and ret, 8; standardisation adds a read of adv and
+    valid (5) and a read of both with a write of adv (9)."""
+    import statistics
+    from cartpoleplusplus_amd import returns
+    dev = torch.device("cuda", 0)
+    K = args.steps
+    gamma, lam = 0.99, 0.95
+
+    def run(fn, calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(calls):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / calls
+
+    def series(fn, calls):
+        run(fn, calls)  # warm-up
+        us = [run(fn, calls) for _ in range(args.repeats)]
+        med = statistics.median(us)
+        return {"us": us, "median_us": med, "spread": (max(us) - min(us)) / med, "calls_per_run": calls}
+
+    out = {"tree": os.path.abspath(_TREE), "steps": K, "repeats": args.repeats, "copy_tbps": args.copy_tbps,
+           "device": torch.cuda.get_device_name(0), "gamma": gamma, "lam": lam, "boundary": "same_step", "sizes": {}}
+    for B, P, G in ((65536, 1, 1), (4096, 16, 256)):
+        g = torch.Generator(device=dev).manual_seed(1234 + B)
+        reward = torch.ones((K, B), device=dev)
+        # ragged episodes of about 50 steps, none longer than 120
+        done = (torch.rand((K, B), device=dev, generator=g) < 0.02)
+        done[119::120] = True
+        done = done.to(torch.uint8)
+        values = torch.randn((K + 1, B), device=dev, generator=g)
+        member = (torch.arange(B, device=dev) // G) % P
+        size = {"batch": B, "population": P, "group": G, "legs": {}}
+        legs = {
+            "episode_total_standardise": (
+                lambda: returns.advantages(reward, done, standardise=True, population=P, group=G),
+                lambda: _torch_advantages(reward, done, "episode_total", gamma, lam, None, member, P), 10 + 5 + 9),
+            "gae": (
+                lambda: returns.advantages(reward, done, "gae", gamma=gamma, lam=lam, values=values),
+                lambda: _torch_advantages(reward, done, "gae", gamma, lam, values, member, P), 10 + 8),
+        }
+        for name, (lib_fn, torch_fn, bytes_per_sample) in legs.items():
+            a, b = lib_fn(), torch_fn()
+            err = (a.adv - b[0]).abs().max().item()      # the same function: the torch sums run in another order
+            same_valid = bool((a.valid == b[1]).all().item())
+            res = {"library": series(lib_fn, 20), "torch": series(torch_fn, 1), "max_abs_diff_to_torch": err,
+                   "valid_equal": same_valid, "bytes_per_sample": bytes_per_sample}
+            nbytes = bytes_per_sample * K * B
+            res["algorithmic_bytes"] = nbytes
+            res["library_tbps"] = nbytes / (res["library"]["median_us"] * 1e-6) / 1e12
+            res["share_of_copy_bandwidth"] = res["library_tbps"] / args.copy_tbps
+            res["torch_over_library"] = res["torch"]["median_us"] / res["library"]["median_us"]
+            res["gate_library_not_slower"] = res["library"]["median_us"] <= res["torch"]["median_us"]
+            size["legs"][name] = res
+            del a, b
+        out["sizes"][f"B{B}_P{P}"] = size
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    if not all(r["gate_library_not_slower"] and r["valid_equal"] for s in out["sizes"].values() for r in s["legs"].values()):
+        raise SystemExit("--returns: the library call is slower than the torch loop, or disagrees with it")
+
+
 def _stacked(W, widths):
     """Packed rows (P, F) as a stacked population [(W (P, out, in), b (P, out)), ...]."""
     out, o = [], 0
@@ -343,6 +465,7 @@ def main():
     ap.add_argument("--population", nargs="?", const="a,b,c,d,e", default=None, help="with --policy: the population legs")
     ap.add_argument("--es", nargs="?", const="d,anti,plain,g8,grad", default=None,
                     help="with --policy: the ES perturbation legs (d, anti, plain, g8, grad)")
+    ap.add_argument("--returns", action="store_true", help="returns and advantages against a torch loop")
     ap.add_argument("--tree", default=None, help="import cartpoleplusplus_amd from this checkout instead of the tool's own")
     ap.add_argument("--copy-tbps", type=float, default=6.29, help="measured copy bandwidth for the weight-streaming floor")
     ap.add_argument("--out", default=None)
@@ -352,6 +475,8 @@ def main():
     ap.add_argument("--ring", type=int, default=1 << 22)
     ap.add_argument("--sample", type=int, default=65536)
     args = ap.parse_args()
+    if args.returns:
+        return returns_bench(args)
     if args.policy and args.es:
         return es_bench(args)
     if args.policy and args.population:
