@@ -408,6 +408,38 @@ class BatchedCartpole:
                      "cp_policy_es_gradient")
         return g
 
+    def policy_gradient(self, obs, actions, coeff, logp=False, logits=False):
+        """lrpg's ascent direction under the discrete policy that is set (cp_policy_gradient): for a window
+        obs (K, B, R, 2, 7) float32, actions (K, B, 2) int8, coeff (K, B) float32 (e.g. advantages().adv),
+        grad[m] = sum over member m's samples of coeff * d log pi(a | obs) / d theta, shaped like
+        self.policy_weights, so `env.policy_weights.add_(lr * grad)` is the update.  Samples with coeff == 0 or
+        an action outside 0..4 are skipped.  logp=True / logits=True also return logp (K, B) and the logits
+        (K, B, 10) the kernel computed: (grad, logp, logits) in that order, those asked for.  Deterministic."""
+        if self.policy is None:
+            raise native.CartpoleError("no policy set (set_policy)")
+        if not isinstance(obs, torch.Tensor) or obs.dim() < 1:
+            raise ValueError("obs: a (K, B, R, 2, 7) float32 device tensor")
+        K = int(obs.shape[0])
+        o = _device_buffer(obs, (K, self.B, self.R, 2, 7), torch.float32, self.device, "obs")
+        a = _device_buffer(actions, (K, self.B, 2), torch.int8, self.device, "actions")
+        c = _device_buffer(coeff, (K, self.B), torch.float32, self.device, "coeff")
+        need = int(self.lib.cp_policy_gradient_scratch_bytes(self.h, K))
+        if need < 0:
+            native.check(self.h, -1, "cp_policy_gradient_scratch_bytes")
+        scratch = getattr(self, "_pg_scratch", None)
+        if scratch is None or scratch.numel() < need:
+            self._pg_scratch = None   # free the old one first
+            scratch = self._pg_scratch = torch.empty(need, device=self.device, dtype=torch.uint8)
+        f32 = dict(device=self.device, dtype=torch.float32)
+        grad = torch.empty_like(self.policy_weights)
+        lp = torch.empty((K, self.B), **f32) if logp else None
+        lg = torch.empty((K, self.B, 2 * abi.CP_NUM_DISCRETE), **f32) if logits else None
+        native.check(self.h, self.lib.cp_policy_gradient(self.h, K, _ptr(o), _ptr(a), _ptr(c), _ptr(lg), _ptr(lp),
+                                                         _ptr(grad), _ptr(scratch), self._stream()),
+                     "cp_policy_gradient")
+        out = (grad,) + ((lp,) if logp else ()) + ((lg,) if logits else ())
+        return out[0] if len(out) == 1 else out
+
     def set_bump_forces(self, forces):
         """Parity mode (bump_mode='host'): LINK-frame bump forces (B, 30, 2, 2).  float64 input goes
         through cp_set_bump_forces64 (an fp64 handle keeps the reference's doubles, an fp32 handle

@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, "csrc", f) for f in ("cp_kernels.hip", "cp_kernels64.hip")]
 DEPS = SRCS + [os.path.join(HERE, "csrc", f) for f in ("cp_common.h", "cp_shapes.h", "cp_env.h", "cp_physics.h",
                                                      "cp_math.h", "cp_raster.h", "cp_replay.h", "cp_returns.h",
-                                                     "cp_policy.h")] + [
+                                                     "cp_policy.h", "cp_policy_grad.h")] + [
     os.path.join(HERE, "..", "include", "cartpole_amd.h")]
 LIB = os.path.join(HERE, "libcartpole_hip.so")
 STAMPS_LIB = os.path.join(HERE, "libcartpole_hip_stamps.so")

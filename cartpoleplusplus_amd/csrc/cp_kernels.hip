@@ -7,7 +7,7 @@
 // over `real` and instantiated here for fp32 (namespace cp, the product path) and in
 // cp_kernels64.hip for fp64 (namespace cp64, the parity variant, cp_config.precision).
 // This file also holds the fp32-only kernels (reset-mask compaction, raster obs, event
-// log records, replay memory, returns and advantages) and every C-ABI entry point (include/cartpole_amd.h).
+// log records, replay memory, returns and advantages, the policy gradient) and every C-ABI entry point (include/cartpole_amd.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +37,7 @@
 #include "cp_raster.h"
 #include "cp_replay.h"
 #include "cp_returns.h"
+#include "cp_policy_grad.h"
 
 namespace cp {
 
@@ -953,6 +954,45 @@ int cp_policy_es_gradient(cp_handle* h, int64_t member_lo, int32_t count, const 
     CP_TRY(h, hipSetDevice(h->device));
     cp::launch_policy_es_gradient(h->es, (int)h->pol.floats, member_lo, count, coeff, h->es_partial, grad_out,
                                   (hipStream_t)stream);
+    CP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+/* ---- the discrete heads' policy gradient (cp_policy_grad.h) ---- */
+// what cp_policy_gradient_scratch_bytes and cp_policy_gradient reject alike; fills the plan
+static int policy_grad_check(const cp_handle* h, int steps, const char* who, cps::PolicyGrad* plan) {
+    cp_handle* const eh = const_cast<cp_handle*>(h);  // the error text only
+    const std::string w = std::string(who) + ": ";
+    if (!h) return fail(nullptr, w + "null handle");
+    if (!h->pol_on) return fail(eh, w + "no policy set (cp_set_policy)");
+    if (policy_kind(h) != CP_ACTION_DISCRETE)
+        return fail(eh, w + "the policy has a continuous head (TANH, CLIP); the gradient is the discrete heads'");
+    if (h->es.kind != CP_ES_OFF)
+        return fail(eh, w + "ES perturbations are on (cp_set_policy_es); their update is cp_policy_es_gradient");
+    if (steps < 1) return fail(eh, w + "steps must be >= 1");
+    if ((int64_t)steps * (int64_t)h->cfg.num_envs > 0x7fffffffll)
+        return fail(eh, w + "steps * num_envs must stay below 2^31 (the sample index)");
+    *plan = cps::policy_grad_plan(h->pol.width, h->pol.num_layers, h->pol.population, h->pol.group, h->cfg.env_id_offset,
+                                  steps, h->cfg.num_envs);
+    return 0;
+}
+
+int64_t cp_policy_gradient_scratch_bytes(const cp_handle* h, int steps) {
+    cps::PolicyGrad plan;
+    if (policy_grad_check(h, steps, "cp_policy_gradient_scratch_bytes", &plan)) return -1;
+    return cps::policy_grad_scratch_bytes(plan, h->pol.floats);
+}
+
+int cp_policy_gradient(cp_handle* h, int steps, const float* obs, const int8_t* actions, const float* coeff,
+                       float* logits_out, float* logp_out, float* grad_out, void* scratch, void* stream) {
+    cps::PolicyGrad plan;
+    if (policy_grad_check(h, steps, "cp_policy_gradient", &plan)) return -1;
+    if (!obs || !actions || !coeff || !grad_out || !scratch)
+        return fail(h, "cp_policy_gradient: null obs, actions, coeff, grad_out or scratch");
+    if ((uintptr_t)scratch & 15) return fail(h, "cp_policy_gradient: scratch must be 16-byte aligned");
+    CP_TRY(h, hipSetDevice(h->device));
+    cp::PolGrad a{obs, actions, coeff, logits_out, logp_out, (float*)scratch};
+    CP_TRY(h, cp::launch_policy_gradient(h->pol, plan, a, grad_out, (hipStream_t)stream));
     CP_TRY(h, hipGetLastError());
     return 0;
 }

@@ -2,7 +2,8 @@
 // the resolver behind cp_create / cp_set_lqr / cp_set_kernel_shape, the checks of cp_set_kernel_shape's
 // requests, and the two facts the launchers (cp_env.h) share with it.  tests/shape_table.cpp pins it on the CPU.
 // Also cp_policy_act's kernel choice for a policy population and the member path's work split, which the kernel
-// (cp_policy.h) and the launcher share; tests/policy_runs.cpp pins those.
+// (cp_policy.h) and the launcher share; tests/policy_runs.cpp pins those.  And cp_policy_gradient's plan (tile size,
+// tiles per member, partial sums), shared by cp_policy_grad.h and the C-ABI; tests/policy_grad_plan.cpp pins it.
 #pragma once
 #include <stddef.h>
 
@@ -158,6 +159,121 @@ inline size_t policy_member_lds_bytes(const int32_t* width, int num_layers, int 
         wmax = w > wmax ? w : wmax;
     }
     return sizeof(float) * ((size_t)2 * amax * policy_env_stride(group, B) + (size_t)((wmax + 3) & ~3));
+}
+
+// ---- cp_policy_gradient's work split (cp_policy_grad.h; DESIGN.md §9.5 "Policy gradient")
+// The window's samples (k, i) of one member run (policy_runs' runs: consecutive local envs with one member) are
+// numbered s = k * len + (i - lo), and a tile is `tile` consecutive s of one run.  A member's tiles are those of its
+// runs r0, r0 + P, ... in run order; `slices` blocks per member take contiguous shares of them and each writes one
+// partial [F], so the scratch is slices * P * F floats.  With one member (population <= 1) the handle is one run.
+constexpr int kPolicyGradThreads = 256;
+constexpr size_t kPolicyGradLdsMax = 160 * 1024;  // a CU's LDS
+constexpr int kPolicyGradMeta = 64 * 24;          // the kernel's static LDS: per tile column index, coeff, 2 actions
+
+struct PolicyGrad {
+    int64_t off, k0;      // env_id_offset (0 with one member); the first run's global group index
+    int32_t P, G, K, B;   // P >= 1; one member: G = B
+    int32_t runs;         // member runs that meet [off, off + B)
+    int32_t first_len, last_len;  // envs of run 0 and of run runs - 1 (the others hold G)
+    int32_t tile, es;     // samples per tile (64, 32 or 16) and the LDS row stride of a tile (floats)
+    int32_t rows;         // LDS rows: every layer's inputs and a row of ones, then the 10 logits
+    int32_t wfloats;      // LDS floats of the widest layer's [W | b] image
+    int32_t slices;       // partial sums per member
+    int64_t tiles_full;   // tiles of a run of G envs
+};
+struct PolicyGradTile {
+    int lo, len;  // the run's local envs [lo, lo + len)
+    int s0, n;    // the tile's samples s0 .. s0 + n - 1 of the run's len * K
+};
+CPS_HD int64_t policy_grad_run_tiles(const PolicyGrad& p, int len) { return ((int64_t)len * p.K + p.tile - 1) / p.tile; }
+CPS_HD int policy_grad_run_len(const PolicyGrad& p, int r) { return r == 0 ? p.first_len : r == p.runs - 1 ? p.last_len : p.G; }
+// member m's first run, or >= runs if it has none
+CPS_HD int64_t policy_grad_first_run(const PolicyGrad& p, int m) { return ((int64_t)m - p.k0 % p.P + p.P) % p.P; }
+CPS_HD int64_t policy_grad_member_tiles(const PolicyGrad& p, int m) {
+    const int64_t r0 = policy_grad_first_run(p, m);
+    if (r0 >= p.runs) return 0;
+    int64_t J = (p.runs - 1 - r0) / p.P + 1, t = 0;  // the member's runs
+    if (r0 == 0) {
+        t += policy_grad_run_tiles(p, p.first_len);
+        --J;
+    }
+    if (p.runs > 1 && (p.runs - 1 - r0) % p.P == 0) {
+        t += policy_grad_run_tiles(p, p.last_len);
+        --J;
+    }
+    return t + J * p.tiles_full;
+}
+// tile t < policy_grad_member_tiles(p, m) of member m
+CPS_HD PolicyGradTile policy_grad_tile(const PolicyGrad& p, int m, int64_t t) {
+    const int64_t r0 = policy_grad_first_run(p, m);
+    int64_t r, within;
+    const int64_t tf = r0 == 0 ? policy_grad_run_tiles(p, p.first_len) : 0;
+    if (t < tf) {
+        r = 0;
+        within = t;
+    } else {
+        const int64_t j = (r0 == 0 ? 1 : 0) + (t - tf) / p.tiles_full;
+        r = r0 + j * p.P;
+        within = (t - tf) % p.tiles_full;
+    }
+    PolicyGradTile x;
+    x.len = policy_grad_run_len(p, (int)r);
+    x.lo = r == 0 ? 0 : (int)((p.k0 + r) * p.G - p.off);
+    const int64_t total = (int64_t)x.len * p.K, s0 = within * p.tile;
+    x.s0 = (int)s0;
+    x.n = (int)(total - s0 < p.tile ? total - s0 : p.tile);
+    return x;
+}
+inline int policy_grad_env_stride(int tile) { return tile % 8 == 0 ? tile + 4 : tile; }
+inline size_t policy_grad_lds_bytes(const int32_t* width, int num_layers, int tile, int* rows_out, int* wfloats_out) {
+    int rows = width[num_layers], wmax = 0;
+    for (int l = 0; l < num_layers; ++l) {
+        rows += width[l] + 1;
+        const int w = policy_weight_floats(width[l], width[l + 1]);
+        wmax = w > wmax ? w : wmax;
+    }
+    wmax = (wmax + 3) & ~3;
+    if (rows_out) *rows_out = rows;
+    if (wfloats_out) *wfloats_out = wmax;
+    return sizeof(float) * ((size_t)rows * policy_grad_env_stride(tile) + (size_t)wmax) + kPolicyGradMeta;
+}
+// The plan of a call that passed cp_policy_gradient's checks (K * B < 2^31, env_id_offset >= 0 with a population).
+// The tile is the largest of 64 / 32 / 16 samples whose LDS lets two blocks share a CU, else the largest that fits
+// one (the widest legal policy, 4 layers of 128 units, fits at 32); slices: a block takes at least 4 tiles of the
+// member with the most, and about 2,048 blocks fill the chip.
+inline PolicyGrad policy_grad_plan(const int32_t* width, int num_layers, int population, int group, int64_t off, int K,
+                                   int B) {
+    PolicyGrad p{};
+    const bool one = population <= 1;
+    p.off = one ? 0 : off;
+    p.P = one ? 1 : population;
+    p.G = one ? B : group;
+    p.K = K;
+    p.B = B;
+    p.k0 = p.off / p.G;
+    p.runs = (int32_t)((p.off + B - 1) / p.G - p.k0) + 1;
+    const int64_t end0 = (p.k0 + 1) * p.G < p.off + B ? (p.k0 + 1) * p.G : p.off + B;
+    p.first_len = (int32_t)(end0 - p.off);
+    p.last_len = p.runs == 1 ? p.first_len : (int32_t)(p.off + B - (p.k0 + p.runs - 1) * p.G);
+    p.tile = 0;
+    for (int pass = 0; pass < 2 && !p.tile; ++pass)
+        for (int t = 64; t >= 16 && !p.tile; t >>= 1)
+            if (policy_grad_lds_bytes(width, num_layers, t, nullptr, nullptr) <= kPolicyGradLdsMax / (pass ? 1 : 2)) p.tile = t;
+    if (!p.tile) p.tile = 16;  // not reached by a policy cp_set_policy accepts
+    p.es = policy_grad_env_stride(p.tile);
+    int rows, wf;
+    policy_grad_lds_bytes(width, num_layers, p.tile, &rows, &wf);
+    p.rows = rows;
+    p.wfloats = wf;
+    p.tiles_full = policy_grad_run_tiles(p, p.G);
+    // an upper bound of a member's tiles
+    const int64_t most = ((int64_t)p.runs + p.P - 1) / p.P * policy_grad_run_tiles(p, p.G < B ? p.G : B);
+    const int64_t want = (most + 3) / 4, cap = p.P >= 2048 ? 1 : 2048 / p.P;
+    p.slices = (int32_t)(want < 1 ? 1 : want < cap ? want : cap);
+    return p;
+}
+inline int64_t policy_grad_scratch_bytes(const PolicyGrad& p, int64_t F) {
+    return ((int64_t)p.slices * p.P * F * (int64_t)sizeof(float) + 15) & ~(int64_t)15;
 }
 
 }  // namespace cps

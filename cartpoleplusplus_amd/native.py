@@ -27,6 +27,7 @@ EXPORTS = (
     "cp_policy_noise_check", "cp_set_policy_noise", "cp_policy_noise_get", "cp_policy_noise_set",
     "cp_policy_es_check", "cp_set_policy_es", "cp_policy_es_weights", "cp_policy_es_gradient",
     "cp_returns_check", "cp_returns_scratch_bytes", "cp_returns_compute",
+    "cp_policy_gradient_scratch_bytes", "cp_policy_gradient",
 )
 
 _lib = None
@@ -100,6 +101,8 @@ def load():
         "cp_returns_check": (I, [P(abi.cp_returns)]),
         "cp_returns_scratch_bytes": (C.c_int64, [P(abi.cp_returns)]),
         "cp_returns_compute": (I, [P(abi.cp_returns)] + [VP] * 13),
+        "cp_policy_gradient_scratch_bytes": (C.c_int64, [VP, I]),
+        "cp_policy_gradient": (I, [VP, I] + [VP] * 8),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

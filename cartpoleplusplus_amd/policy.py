@@ -147,3 +147,28 @@ def repack(packed, layers):
         raise ValueError(f"policy: {flat.numel()} floats for a packed tensor of {packed.numel()}")
     packed.copy_(flat)
     return packed
+
+
+def unpack(packed_row, like):
+    """The inverse of repack: [(W (out, in), b (out,)), ...] views of one packed row (F,), for the architecture
+    of `like` (an nn.Sequential, a list of (W, b) pairs, or a list of widths (in, h1, .., out)).  With `like` a
+    module, its parameters are also overwritten with the row's values (a checkpoint loaded back into torch)."""
+    if isinstance(like, (list, tuple)) and like and all(isinstance(w, int) for w in like):
+        widths = list(like)
+    else:
+        widths, _ = _flat(like)
+    row = packed_row.reshape(-1)
+    n = sum(o * (i + 1) for i, o in zip(widths[:-1], widths[1:]))
+    if row.numel() != n:
+        raise ValueError(f"policy: a packed row of {row.numel()} floats for widths {widths} ({n} floats)")
+    out, at = [], 0
+    for i, o in zip(widths[:-1], widths[1:]):
+        out.append((row[at:at + o * i].view(o, i), row[at + o * i:at + o * i + o]))
+        at += o * i + o
+    if isinstance(like, torch.nn.Module):
+        with torch.no_grad():
+            for (W, b), (Wm, bm) in zip(out, _layers(like)):
+                Wm.copy_(W)
+                if isinstance(bm, torch.nn.Parameter):
+                    bm.copy_(b)
+    return out

@@ -444,6 +444,46 @@ int cp_policy_es_weights(cp_handle* h, int64_t member_lo, int32_t count, float* 
 int cp_policy_es_gradient(cp_handle* h, int64_t member_lo, int32_t count, const float* coeff, float* grad_out,
                           void* stream);
 
+/* ---- Policy gradient of the discrete heads (lrpg_cartpole.py:105-121; lrpg's update without a torch mirror) ----
+ * For a window of K rows of samples, per population member m and packed parameter f,
+ *     grad_out[m][f] = sum over the member's samples n of coeff_n * d log pi(a_n | obs_n) / d theta_f,
+ * the ascent direction of lrpg's objective, in the layout of cp_policy.weights ([P][F], P = max(population, 1)):
+ * weights += lr * grad is the whole update.  All buffers are the caller's device pointers: obs [K][B][R][2][7],
+ * actions [K][B][2] int8, coeff [K][B], logits_out [K][B][10] or NULL, logp_out [K][B] or NULL.  The call
+ * allocates nothing, never synchronises the host and can be captured into a graph; it reads no env state and
+ * changes none.  Of the handle it uses B, R, env_id_offset and the policy that is set, whose weights it reads
+ * live from cp_policy.weights.  ABI 8, additive.
+ *
+ *   1. Sample (k, i) is row k of env i; its member is ((env_id_offset + i) / group) % population in 64-bit
+ *      arithmetic (the populations' rule); population <= 1: one member.
+ *   2. A sample is skipped if its coeff is exactly 0 (+-0) or either action is outside 0..4.  A skipped sample is
+ *      not evaluated: its logp_out is 0, its logits_out row is 0 and it adds nothing to grad_out, whatever its
+ *      obs row holds (NaN, inf).  This covers cp_returns_compute's valid == 0 samples, whose adv is 0.
+ *   3. The forward pass is cp_policy_act's, bit for bit: per unit acc = b[j], then acc = fmaf(W[j][i], x[i], acc)
+ *      for i ascending, hidden units acc > 0 ? acc : 0.  logits_out is the last layer's z.
+ *   4. The log-probability, all fp32, each operation rounded on its own.  Per cart c: m = max_j z_j,
+ *      e_j = expf(z_j - m), S = e_0 + e_1 + e_2 + e_3 + e_4 in that order, lp_c = (z_a - m) - logf(S);
+ *      logp = lp_0 + lp_1.  epsilon is ignored: lrpg differentiates the softmax, not the epsilon-greedy mixture,
+ *      and ARGMAX and SAMPLE heads are treated alike.
+ *   5. The backward pass: dz_{c,j} = coeff * ((j == a_c ? 1 : 0) - e_j / S); a hidden unit passes gradient iff
+ *      its forward acc > 0; dW[j][i] = sum delta_j x_i, db[j] = sum delta_j.  The sum, not the mean.
+ *   6. Everything accumulates in fp32.  The summation order is the library's choice, but a fixed function of
+ *      (K, B, R, the architecture, population, group, env_id_offset): no floating-point atomics, so two equal
+ *      calls give equal bits.
+ *   7. A member without an evaluated sample gets an all-zero row.
+ *   8. scratch is 16-byte aligned and holds `partials` partial sums [P][F] per member, added in partial order:
+ *      cp_policy_gradient_scratch_bytes = partials * P * F * 4 rounded up to a multiple of 16, with no header,
+ *      so partials = bytes / (P * F * 4) rounded up.  partials depends on K, B, the architecture, population,
+ *      group and env_id_offset only (at most 2,048 / P, at least 1).
+ *
+ * Rejected, with the cause in cp_last_error: no policy set; a continuous head (TANH, CLIP); ES on (its update
+ * is cp_policy_es_gradient); steps < 1; steps * B >= 2^31; NULL obs, actions, coeff, grad_out or scratch; a
+ * scratch that is not 16-byte aligned; for cp_policy_gradient_scratch_bytes also a NULL handle (it launches
+ * nothing; < 0 on error). */
+int64_t cp_policy_gradient_scratch_bytes(const cp_handle* h, int steps);
+int cp_policy_gradient(cp_handle* h, int steps, const float* obs, const int8_t* actions, const float* coeff,
+                       float* logits_out, float* logp_out, float* grad_out, void* scratch, void* stream);
+
 /* Optional per-substep 12-state readback of both poles (bullet_cartpole.py:212-234,
  * exposed there as monkey_positions / monkey_velocities):
  * float32 [B][2 poles][R][S][4][3] = (xyz, rpy, linvel, angvel).  Enabled when

@@ -29,7 +29,10 @@ with the same code (the P = 1 gate: run the two alternately in one session).  --
 
 --policy --es [LEGS]: the seeded ES perturbation legs (DESIGN.md §9.5 "ES perturbations"; es_bench below).
 
---returns: returns and advantages of a rollout window (DESIGN.md §9.5 "Returns and advantages"; returns_bench below)."""
+--returns: returns and advantages of a rollout window (DESIGN.md §9.5 "Returns and advantages"; returns_bench below).
+
+--policy-gradient: cp_policy_gradient against today's torch update (DESIGN.md §9.5 "Policy gradient";
+policy_gradient_bench below)."""
 import argparse
 import json
 import os
@@ -375,6 +378,108 @@ def returns_bench(args):
         raise SystemExit("--returns: the library call is slower than the torch loop, or disagrees with it")
 
 
+def policy_gradient_bench(args):
+    """--policy-gradient: BatchedCartpole.policy_gradient against the torch path it replaces (forward, loss, backward,
+    repack on a torch mirror of the net), in one process on one build, at B = --batch, R = 3, K = --steps, lrpg's
+    "100,50" net, the ragged valid mask of --returns' done pattern (coeff = the standardised episode totals, 0
+    where invalid).  Legs: P = 1, and P = 16 with G = B / 16 (torch: one forward / backward / repack per member).
+    ms per call: one warm-up run and the median of --repeats runs, spread = (max - min) / median; the peak allocated
+    memory of each leg above what it starts with.  FLOPs 6 F N (N the evaluated samples: forward, dW and W^T delta,
+    2 F each) against --fp32-tflops; bytes: the obs, actions and coeff read once, logp never written."""
+    import statistics
+    from cartpoleplusplus_amd import policy
+    dev = torch.device("cuda", 0)
+    B, K, R = args.batch, args.steps, 3
+    widths = (14 * R, 100, 50, 10)
+    F = sum(o * (i + 1) for i, o in zip(widths[:-1], widths[1:]))
+    g = torch.Generator(device=dev).manual_seed(4321)
+
+    def make_net():
+        return torch.nn.Sequential(torch.nn.Linear(widths[0], 100), torch.nn.ReLU(), torch.nn.Linear(100, 50), torch.nn.ReLU(),
+                                   torch.nn.Linear(50, 10)).to(dev)
+
+    env = BatchedCartpole(B, 0, action_repeats=R, initial_force=55.0, autoreset=True, seed=1234)
+    obs = torch.randn((K, B, R, 2, 7), device=dev, generator=g)
+    act = torch.randint(0, 5, (K, B, 2), dtype=torch.int8, device=dev, generator=g)
+    reward = torch.ones((K, B), device=dev)
+    done = (torch.rand((K, B), device=dev, generator=g) < 0.02)
+    done[119::120] = True
+    done = done.to(torch.uint8)
+
+    def run(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    def series(fn):
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        run(fn)  # warm-up
+        ms = [run(fn) for _ in range(args.repeats)]
+        med = statistics.median(ms)
+        return {"ms": ms, "median_ms": med, "spread": (max(ms) - min(ms)) / med,
+                "peak_extra_bytes": torch.cuda.max_memory_allocated() - base}
+
+    out = {"tree": os.path.abspath(_TREE), "batch": B, "steps": K, "repeats": args.repeats, "floats": F,
+           "device": torch.cuda.get_device_name(0), "fp32_tflops": args.fp32_tflops, "copy_tbps": args.copy_tbps, "legs": {}}
+    for P in (1, 16):
+        G = B // P
+        nets = [make_net() for _ in range(P)]
+        if P == 1:
+            env.set_policy(nets[0], "sample", epsilon=0.05, seed=7)
+        else:
+            env.set_policy(nets, "sample", epsilon=0.05, seed=7, group=G)
+        adv = env.advantages(reward, done, standardise=True, population=P, group=G)
+        coeff, valid = adv.adv, adv.valid.bool()
+        N = int((coeff != 0).sum().item())
+        rows = [env.policy_weights[m] if P > 1 else env.policy_weights for m in range(P)]
+
+        def lib_fn():
+            return env.policy_gradient(obs, act, coeff)
+
+        def torch_fn():
+            for m in range(P):
+                sl = slice(m * G, (m + 1) * G)
+                v = valid[:, sl]
+                net = nets[m]
+                net.zero_grad(set_to_none=True)
+                logp = torch.log_softmax(net(obs[:, sl][v].reshape(-1, widths[0])).view(-1, 2, 5), -1)
+                chosen = logp.gather(-1, act[:, sl][v].long().unsqueeze(-1)).squeeze(-1).sum(-1)
+                loss = -(chosen * coeff[:, sl][v]).mean()
+                loss.backward()
+                policy.repack(rows[m], net)
+
+        lib, tor = series(lib_fn), series(torch_fn)
+        # the same function: -n_m * the mean loss's gradient is the library's sum
+        gl = lib_fn().reshape(P, -1)
+        torch_fn()
+        gt = torch.stack([-float(valid[:, m * G:(m + 1) * G].sum().item()) * torch.cat(
+            [t.grad.reshape(-1) for lin in nets[m] if isinstance(lin, torch.nn.Linear) for t in (lin.weight, lin.bias)])
+            for m in range(P)])
+        leg = {"population": P, "group": G, "evaluated_samples": N, "library": lib, "torch": tor,
+               "max_rel_diff_to_torch": ((gl - gt).abs().max() / gt.abs().max()).item(),
+               "scratch_bytes": int(env.lib.cp_policy_gradient_scratch_bytes(env.h, K))}
+        leg["torch_over_library"] = tor["median_ms"] / lib["median_ms"]
+        leg["library_tflops"] = 6.0 * F * N / (lib["median_ms"] * 1e-3) / 1e12
+        leg["share_of_fp32_peak"] = leg["library_tflops"] / args.fp32_tflops
+        nbytes = N * (widths[0] * 4) + K * B * (2 + 4)
+        leg["algorithmic_bytes"] = nbytes
+        leg["library_tbps"] = nbytes / (lib["median_ms"] * 1e-3) / 1e12
+        leg["share_of_copy_bandwidth"] = leg["library_tbps"] / args.copy_tbps
+        out["legs"][f"P{P}"] = leg
+        del nets, gl, gt, adv
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def _stacked(W, widths):
     """Packed rows (P, F) as a stacked population [(W (P, out, in), b (P, out)), ...]."""
     out, o = [], 0
@@ -466,6 +571,8 @@ def main():
     ap.add_argument("--es", nargs="?", const="d,anti,plain,g8,grad", default=None,
                     help="with --policy: the ES perturbation legs (d, anti, plain, g8, grad)")
     ap.add_argument("--returns", action="store_true", help="returns and advantages against a torch loop")
+    ap.add_argument("--policy-gradient", action="store_true", help="cp_policy_gradient against the torch update")
+    ap.add_argument("--fp32-tflops", type=float, default=157.0, help="the fp32 vector peak for --policy-gradient's share")
     ap.add_argument("--tree", default=None, help="import cartpoleplusplus_amd from this checkout instead of the tool's own")
     ap.add_argument("--copy-tbps", type=float, default=6.29, help="measured copy bandwidth for the weight-streaming floor")
     ap.add_argument("--out", default=None)
@@ -477,6 +584,8 @@ def main():
     args = ap.parse_args()
     if args.returns:
         return returns_bench(args)
+    if args.policy_gradient:
+        return policy_gradient_bench(args)
     if args.policy and args.es:
         return es_bench(args)
     if args.policy and args.population:
